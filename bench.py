@@ -8,6 +8,10 @@ Data: synthetic (seeded smooth images, random-init weights of the real architect
 [1, 77, 1024] text context) — no datasets or checkpoints offline.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--size 512] [--ddim-steps 2]
+                  [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds the
+untimed legs: the launch-profiler roofline pass, the fp32 parity-mode leg and the CPU baseline.
+--dump-outputs DIR writes the last timed step's outputs (same arguments, same inputs every run).
 For N > 1 either run it as is (it starts N ranks itself: rdeic_amd/launch.py) or under
 torch.distributed.run with --nproc-per-node N (WORLD_SIZE must equal --gpus); one process per GPU, RCCL.
 """
@@ -81,8 +85,17 @@ def parse(argv=None):
                          "batch's host rANS coding and small entropy-stage kernels overlap another batch's GPU work")
     ap.add_argument("--splitk-rule", default=None, metavar="BLOCKS,MAX",
                     help="inference split-K rule of the small-M convs (A/B only; ops.SPLITK_BLOCKS / SPLITK_MAX)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the launch-profiler roofline pass, the fp32 parity-mode leg and "
+                         "the CPU baseline (each with its own switch below); a plain run only sets up, warms up, times "
+                         "--steps steps and prints the result line with roofline / cpu_baseline / fp32_parity_mode null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / "
+                         "float64): images (the decoded uint8 pixels), body_bytes (bytes per file body), bodies (every "
+                         "body's bytes, concatenated) and metrics (the per-image rows); an array past the size budget "
+                         "is stored as a fixed seeded sample beside its <name>_index.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--prof-every", type=int, default=8,
                     help="roofline timing: every launch >= 50 GFLOP (64 MB for GroupNorm), and a hashed "
                          "1-in-N sample of the smaller ones (weighted estimate)")
@@ -97,10 +110,39 @@ def parse(argv=None):
     ap.add_argument("--rate-gain", type=float, default=None,
                     help="synthetic bpp knob (rdeic_amd/weights.py); default: the ~0.08 bpp gain of config 2")
     ap.add_argument("--fp32-steps", type=int, default=2,
-                    help="one-GPU runs with --dtype bf16: also time this many steps of the fp32 parity mode (the "
+                    help="with --full, one-GPU runs with --dtype bf16: also time this many steps of the fp32 parity mode (the "
                          "path whose bitstreams and pixels match the reference) on the same images, and report "
                          "its throughput and the bf16-vs-fp32 bpp / PSNR / MS-SSIM gap; 0 = skip")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed steps)")
+    return args
+
+
+DUMP_BUDGET_BYTES = 56 << 20  # every file of one --dump-outputs DIR together stays under 64 MB
+
+
+def dump_outputs(dirname: str, suffix: str, arrays: dict):
+    """--dump-outputs: DIR/<name><suffix>.npy for each array, as float32 (float64 for arrays that are
+    float64 already). The smallest arrays are written first and each may use an equal share of what
+    is left of the byte budget; an array past its share is stored as a sample at fixed seeded
+    positions of the flattened array (a function of its size alone), with the positions in
+    <name>_index<suffix>.npy, so two builds write comparable files."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    order = sorted(arrays, key=lambda n: arrays[n].size)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            k = share // (a.itemsize + 8)  # the float64 positions count against the budget too
+            idx = np.sort(np.random.default_rng(231).integers(0, a.size, size=k, dtype=np.int64))
+            np.save(os.path.join(dirname, f"{name}_index{suffix}.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            left -= idx.size * 8
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+        left -= a.nbytes
 
 
 def sweep_points(args):
@@ -180,7 +222,8 @@ def main():
         ops.call("rdeic_image_mse", imgs.data_ptr(), out.data_ptr(), B, S * S * 3, mse.data_ptr(), ops.stream_ptr())
         m = mse.cpu().numpy()
         _, ms = quality.ssim_ms_ssim(out, imgs)  # on the device (rdeic_image_ssim)
-        sess._last_out = out  # the step's u8 images (bf16-vs-fp32 pixel PSNR of the fp32 leg)
+        # the step's u8 images and file bodies (--dump-outputs; bf16-vs-fp32 pixel PSNR of the fp32 leg)
+        sess._last_out, sess._last_bodies = out, bodies
         return torch.tensor([[len(b) * 8.0 / (S * S), float(len(b)),
                               10 * math.log10(255.0 ** 2 / max(float(v), 1e-10)), float(v), float(q), 1.0, float(rank)]
                              for b, v, q in zip(bodies, m, ms)], dtype=torch.float32)
@@ -234,8 +277,11 @@ def main():
         parallel.barrier(dev)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        # what the last timed step returned (copied now: the roofline pass below runs session 0 again)
+        last = sessions[(args.steps - 1) % nsess]
+        last_out, last_bodies = last._last_out.clone(), list(last._last_bodies)
         prof = None
-        if headline and not args.no_roofline:
+        if headline and args.full and not args.no_roofline:
             # Roofline pass (untimed): the same steps on ONE session with the native launch profiler
             # (HIP events on the launch stream; launches >= 50 GFLOP always, smaller ones 1 in
             # --prof-every), so each kernel's duration is its own and not shared with a concurrent
@@ -254,16 +300,23 @@ def main():
                         _attn_shapes={k: ops.prof_read_keys(k) for k in ("attention", "attention_dh16", "attention_d512")})
         elapsed = parallel.max_over_ranks(elapsed, dev)
         mrows = metrics.cpu().numpy()
-        last_out = sessions[(args.steps - 1) % nsess]._last_out
-        del sessions
+        del sessions, last
         return {"target_bpp": target, "rate_gain": rate_gain, "elapsed": elapsed, "prof": prof, "out": last_out,
+                "bodies": last_bodies,
                 "mean_bpp": float(mrows[:, 0].mean()), "mean_psnr_db": float(mrows[:, 2].mean()),
                 "mean_ms_ssim": float(mrows[:, 4].mean()),
                 "images": int(mrows.shape[0]), "rows": rows_by_step[-1].numpy()}
 
     results = run_sweep(points, main_i, measure)
+    if args.dump_outputs:
+        r = results[main_i]
+        dump_outputs(args.dump_outputs, "" if world == 1 else f"_rank{rank}",
+                     {"images": r["out"].cpu().numpy(), "body_bytes": np.array([len(b) for b in r["bodies"]]),
+                      "bodies": np.frombuffer(b"".join(bytes(b) for b in r["bodies"]), dtype=np.uint8),
+                      "metrics": r["rows"]})
+        log(f"last timed step's outputs written to {args.dump_outputs}")
     fp32_leg = None
-    if world == 1 and args.dtype == "bf16" and args.fp32_steps > 0 and not args.bpp_sweep:
+    if args.full and world == 1 and args.dtype == "bf16" and args.fp32_steps > 0 and not args.bpp_sweep:
         log(f"fp32 parity mode: 1 warm-up + {args.fp32_steps} timed steps on one session, same images")
         rg = results[main_i]["rate_gain"]
         del model
@@ -362,7 +415,7 @@ def main():
     cpu = None
     if world > 1:
         cpu = {"value": None, "note": "reported on rank 0 of the one-GPU run only (bench.py --gpus 1)"}
-    elif not args.no_cpu_baseline:
+    elif args.full and not args.no_cpu_baseline:
         log("cpu baseline (oracle restatement on the host cores)")
         try:
             from oracle.bench_cpu import run_cpu_baseline

@@ -12,7 +12,7 @@ done
 for i in $(seq 1 $N); do
   for T in A B C; do
     case $T in A) F=$2;; B) F=$3;; C) F=$4;; esac
-    RDEIC_LIB=$PWD/$F timeout -k 10 300 python -u bench.py --steps 8 --warmup 2 --no-cpu-baseline --fp32-steps 0 > $O/$T$i.json 2> $O/$T$i.err || { echo "bench $T$i failed"; tail -5 $O/$T$i.err; exit 1; }
+    RDEIC_LIB=$PWD/$F timeout -k 10 300 python -u bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --fp32-steps 0 > $O/$T$i.json 2> $O/$T$i.err || { echo "bench $T$i failed"; tail -5 $O/$T$i.err; exit 1; }
     python3 -c "import json,sys; d=json.loads(open('$O/$T$i.json').read().strip().splitlines()[-1]); print('$T$i', d['value'], d['ms_per_step'], d['roofline']['ms_per_step'], d['roofline']['frac'])"
   done
 done
