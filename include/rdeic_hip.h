@@ -105,6 +105,21 @@ int rdeic_conv2d_tile(const rdeic_conv_desc* d, int32_t tile, void* stream);
  * bf16 or fp32, no GN prologue, out_mode 0, batch 1, cout % 8 == 0. Not bit-identical to
  * rdeic_conv2d (different k grouping): not for the entropy-model nets. */
 int rdeic_conv2d_splitk(const rdeic_conv_desc* d, int32_t splits, float* ws, size_t ws_floats, void* stream);
+/* The fused nearest-x2 upsample 3x3 conv (up2 = 1, pad 1, ho = 2h, wo = 2w) as four folded 2x2 phase convs in
+ * one LDS-DMA launch: output pixel (2i + a, 2j + b) is a 2x2 conv of the raw input with W_ab = R_a W R_b^T,
+ * R_0 = [[1,0,0],[0,1,1]], R_1 = [[1,1,0],[0,0,1]], zero padding (top, left) = (1 - a, 1 - b): 4/9 of the MACs.
+ * d is the descriptor of rdeic_conv2d for that layer, except that d->weight is the folded pack: four matrices
+ * [cout][wld = 4 * c0] (k = (dy, dx) row-major, then channel), phase 2a + b at + phase * phase_stride elements;
+ * the bias is shared. The results differ from rdeic_conv2d's by the rounding of the folded weights only.
+ * Eligible: bf16 in and out, c1 = 0, c0 % 64 == 0, out_mode 0, batch 1, no gn_ab / emb / res / ln_rows,
+ * 16-byte-aligned rows. Images are launched in groups whose input and output spans stay below 2 GiB
+ * (rdeic_conv2d_up2_group: images per group, 0 = one image is too large). gn_part as rdeic_conv2d (fused where
+ * h * w % 64 == 0: the partial of (image, phase, 64-row group g) is slot image * (4hw/64) + phase * (hw/64) + g).
+ * tile: 25, 26, 30, 32, 33, 36 of rdeic_conv2d_tile, anything else = heuristic.
+ * Returns 0, 1 = not eligible or switched off (rdeic_set_conv_option key 11; nothing was launched: run
+ * rdeic_conv2d with the 3x3 weights), or a negative error. */
+int rdeic_conv2d_up2_phases(const rdeic_conv_desc* d, int64_t phase_stride, int32_t tile, void* stream);
+int rdeic_conv2d_up2_group(const rdeic_conv_desc* d);
 /* 2 (default): bf16 convs without a GN prologue pick among the big register-staged tiles
  * (256x256 / 256x128 / 128x256 / 128x128 / 64x128 / 128x64); 0: the 128-tile kernel with the
  * fused GroupNorm prologue everywhere (A/B timing, debugging). Results are bit-identical.
@@ -127,6 +142,7 @@ int rdeic_set_conv_path(int32_t path);
  * key 10: the VAE edge convs (conv_edge.hip): conv_in from 8 input channels on direct-load MFMA fragments
  *        (bit-identical to the register tile) and norm -> SiLU -> conv to <= 16 channels (fp32 rounding of the
  *        sums differs from the tiny-cout kernel): 1 on (default), 0 off.
+ * key 11: rdeic_conv2d_up2_phases on (1, default) / off (0: it returns 1 and callers run the fused gather).
  * Returns the previous value, or -22 for an unknown key. Results are bit-identical either way
  * (keys 0-5; 6 and 8 change fp32 rounding only). */
 int rdeic_set_conv_option(int32_t key, int32_t value);

@@ -72,6 +72,8 @@ PROTOTYPES = {
     "rdeic_conv2d": (C.c_int, [C.POINTER(ConvDesc), _p]),
     "rdeic_conv2d_splitk": (C.c_int, [C.POINTER(ConvDesc), _i32, _p, C.c_size_t, _p]),
     "rdeic_conv2d_tile": (C.c_int, [C.POINTER(ConvDesc), _i32, _p]),
+    "rdeic_conv2d_up2_phases": (C.c_int, [C.POINTER(ConvDesc), _i64, _i32, _p]),
+    "rdeic_conv2d_up2_group": (C.c_int, [C.POINTER(ConvDesc)]),
     "rdeic_prof_start": (C.c_int, [_i32, _i32]),
     "rdeic_prof_stop": (C.c_int, []),
     "rdeic_launch_count": (C.c_int64, [_i32]),
@@ -221,3 +223,16 @@ def call(name: str, *args, tag=None) -> None:
         RECORDER.append((name, fn, args, tag))
     rc = fn(*args)
     check(name, rc)
+
+
+def call_soft(name: str, *args, tag=None) -> bool:
+    """call() for an entry point that may decline with status 1 before it launches anything
+    (rdeic_conv2d_up2_phases): False then, and nothing is recorded; True after a launch."""
+    fn = getattr(load(), name)
+    rc = fn(*args)
+    if rc == 1:
+        return False
+    check(name, rc)
+    if RECORDER is not None:
+        RECORDER.append((name, fn, args, tag))
+    return True

@@ -114,10 +114,37 @@ struct RowsFrom {
   __device__ __forceinline__ int operator()(int r) const { return m0 + r; }
 };
 
-template <int BM, int BN, int WGM, int WGN, int NT, int P = 2, class RowMap = RowsFrom, bool PF = true>
+// GEMM row m -> output pixel (the row of out / res) and -> the 64-row block's slot in the fused statistics.
+// PixSame: the output rows are the GEMM rows (every conv but the phase launch below).
+struct PixSame {
+  __device__ __forceinline__ long operator()(int m) const { return m; }
+  __device__ __forceinline__ long slot(int row0, int m) const { return (row0 + m) / 64; }
+};
+// The nearest-x2 upsample conv as four folded 2x2 phase convs (rdeic_conv2d_up2_phases): GEMM row
+// m = (img, i, j) of phase (a, b) over the h x w source is output pixel (img, 2i + a, 2j + b) of the 2h x 2w
+// output. Statistics: the partial of (img, phase, 64-row group g) goes to slot img * (4hw/64) + phase * (hw/64) + g
+// (sums over an image do not depend on the pixel order; hw % 64 == 0, so a group never straddles two images).
+struct PixPhase {
+  int h, w, pa, pb;
+  __device__ __forceinline__ long operator()(int m) const {
+    const int hw = h * w;
+    const int img = m / hw, rem = m - img * hw;
+    const int i = rem / w, j = rem - i * w;
+    return ((long)img * (2 * h) + (2 * i + pa)) * (2 * w) + (2 * j + pb);
+  }
+  __device__ __forceinline__ long slot(int row0, int m) const {
+    const int b64 = (h * w) / 64;
+    const int r = (row0 + m) / 64;
+    const int img = r / b64, g = r - img * b64;
+    return (long)img * (4 * b64) + (2 * pa + pb) * b64 + g;
+  }
+};
+
+template <int BM, int BN, int WGM, int WGN, int NT, int P = 2, class RowMap = RowsFrom, bool PF = true,
+          class PixMap = PixSame>
 __device__ __forceinline__ void epilogue_vec(const f32x4 (&acc)[BM / WGM / 16][BN / WGN / 16], const ConvArgs& a,
                                              int m0, int n0, int wm, int wn, int lane, int tid, char* lds,
-                                             RowMap rmap = RowMap{0}) {
+                                             RowMap rmap = RowMap{0}, PixMap pmap = PixMap{}) {
   if constexpr (__is_same(RowMap, RowsFrom)) rmap.m0 = m0;
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
   constexpr int TM = WTM / 16, TN = WTN / 16;
@@ -185,7 +212,7 @@ __device__ __forceinline__ void epilogue_vec(const f32x4 (&acc)[BM / WGM / 16][B
       lpf[k] = float2{0.f, 0.f};
       if (ok) {
         if (a.res && !of32 && a.out_mode != 2)
-          rpf[k] = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.res) + (long)m * a.res_ld + nn);
+          rpf[k] = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.res) + pmap(m) * a.res_ld + nn);
         if (a.ln_rows) lpf[k] = reinterpret_cast<const float2*>(a.ln_rows)[m];
       }
     }
@@ -270,20 +297,20 @@ __device__ __forceinline__ void epilogue_vec(const f32x4 (&acc)[BM / WGM / 16][B
       }
       if (a.res) {
         if (of32) {
-          const float4 r0 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.res) + (long)m * a.res_ld + nn);
-          const float4 r1 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.res) + (long)m * a.res_ld + nn + 4);
+          const float4 r0 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.res) + pmap(m) * a.res_ld + nn);
+          const float4 r1 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.res) + pmap(m) * a.res_ld + nn + 4);
           v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w; v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
         } else {
           bf16 rv[8];
           *reinterpret_cast<uint4*>(rv) =
               k < NPF ? rpf[k < NPF ? k : 0]
-                      : *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.res) + (long)m * a.res_ld + nn);
+                      : *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.res) + pmap(m) * a.res_ld + nn);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += to_f32(rv[e]);
         }
       }
       if (of32) {
-        float* o = reinterpret_cast<float*>(a.out) + (long)m * a.out_ld + nn;
+        float* o = reinterpret_cast<float*>(a.out) + pmap(m) * a.out_ld + nn;
         *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
         *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
         if (st) {  // stored values back over the parked accumulators, for the statistics scan
@@ -294,7 +321,7 @@ __device__ __forceinline__ void epilogue_vec(const f32x4 (&acc)[BM / WGM / 16][B
         bf16 ov[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) ov[e] = from_f32<bf16>(v[e]);
-        *reinterpret_cast<uint4*>(reinterpret_cast<bf16*>(a.out) + (long)m * a.out_ld + nn) = *reinterpret_cast<uint4*>(ov);
+        *reinterpret_cast<uint4*>(reinterpret_cast<bf16*>(a.out) + pmap(m) * a.out_ld + nn) = *reinterpret_cast<uint4*>(ov);
         if (st) {
           *reinterpret_cast<float4*>(L + pr * SDW + cc * 8) =
               make_float4(to_f32(ov[0]), to_f32(ov[1]), to_f32(ov[2]), to_f32(ov[3]));
@@ -345,7 +372,7 @@ __device__ __forceinline__ void epilogue_vec(const f32x4 (&acc)[BM / WGM / 16][B
         const int b = (tid + u * NT) / BN, j = (tid + u * NT) % BN;
         const int nn = n0 + j;
         if (b < BM / 64 && nn < a.cout && rmap(b * 64) < a.M) {  // blocks past M are not in the buffer
-          float* pp = a.gn_part + 4 + ((long)((a.gn_row0 + rmap(b * 64)) / 64) * a.cout + nn) * 2;
+          float* pp = a.gn_part + 4 + (pmap.slot(a.gn_row0, rmap(b * 64)) * a.cout + nn) * 2;
           pp[0] = ((sg[u][0] + sg[u][1]) + sg[u][2]) + sg[u][3];
           pp[1] = ((qg[u][0] + qg[u][1]) + qg[u][2]) + qg[u][3];
         }
@@ -525,7 +552,7 @@ __device__ __forceinline__ void wait_vm_rt(int n) {
 }
 
 // process-wide switches (rdeic_set_conv_option / rdeic_set_conv_path), defined in conv_gemm.hip
-extern int g_conv_path, g_epi_vec, g_swz, g_force_tile, g_dma, g_halo, g_halo8, g_edge;
+extern int g_conv_path, g_epi_vec, g_swz, g_force_tile, g_dma, g_halo, g_halo8, g_edge, g_up2_phases;
 
 // cross-unit entry points
 int make_args(const rdeic_conv_desc* d, ConvArgs& a, bool& vec);                                     // conv_gemm.hip
@@ -536,4 +563,7 @@ int dma_grouped(const rdeic_conv_desc* d, int tile, hipStream_t s, bool* fused =
 bool halo_ok(const rdeic_conv_desc* d, const ConvArgs& a);                                          // conv_halo.hip
 int launch_halo(const rdeic_conv_desc* d, ConvArgs a, hipStream_t s, bool* fused);
 int launch_edge(const rdeic_conv_desc* d, const ConvArgs& a, hipStream_t s, bool* fused);  // conv_edge.hip
+int up2_phase_group(const rdeic_conv_desc* d);                                            // conv_dma.hip
+bool up2_phases_ok(const rdeic_conv_desc* d, long phase_stride);
+int launch_up2_phases(const rdeic_conv_desc* d, long phase_stride, int tile, hipStream_t s, bool* fused);
 }  // namespace rdeic_conv

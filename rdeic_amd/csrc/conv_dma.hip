@@ -26,9 +26,9 @@ namespace rdeic_conv {
 
 // Per-element epilogue straight from the accumulators (tails, PixelShuffle stores, fp32 outputs
 // the vector epilogue does not take).
-template <int TM, int TN, int WTM, int WTN>
+template <int TM, int TN, int WTM, int WTN, class PixMap = PixSame>
 __device__ __forceinline__ void epilogue_scalar(const f32x4 (&acc)[TM][TN], const ConvArgs& a, int m0, int n0, int wm,
-                                                int wn, int lane) {
+                                                int wn, int lane, PixMap pmap = PixMap{}) {
   if (a.out_mode == 2) return;  // unreachable: the host admits GEGLU only where the vector epilogue runs
   const int lrow = lane & 15, lq = lane >> 4;
   const int hw_o = a.ho * a.wo;
@@ -58,8 +58,8 @@ __device__ __forceinline__ void epilogue_scalar(const f32x4 (&acc)[TM][TN], cons
           oidx = p * a.out_ld + c;
           ridx = p * a.res_ld + c;
         } else {
-          oidx = (long)m * a.out_ld + nn;
-          ridx = (long)m * a.res_ld + nn;
+          oidx = pmap(m) * a.out_ld + nn;
+          ridx = pmap(m) * a.res_ld + nn;
         }
         if (a.res) v += of32 ? reinterpret_cast<const float*>(a.res)[ridx] : to_f32(reinterpret_cast<const bf16*>(a.res)[ridx]);
         if (of32) reinterpret_cast<float*>(a.out)[oidx] = v;
@@ -72,7 +72,11 @@ __device__ __forceinline__ void epilogue_scalar(const f32x4 (&acc)[TM][TN], cons
 // 64-deep k-tiles: 128-byte LDS rows, two 16x16x32 MFMA k-steps per tile.
 // GEG: the fused-GEGLU instantiation (out_mode 2, epilogue_geglu); the others compile epilogue_vec only, so the
 // GEGLU epilogue's registers never count against the plain tiles
-template <int BM, int BN, int WGM, int WGN, int S, int EP, bool GEG = false>
+// PH: the phase launch of a nearest-x2 upsample 3x3 conv (rdeic_conv2d_up2_phases). The tile id carries the
+// phase (a, b) between the M and the N tile index; the block runs the 2x2 conv of that phase over the raw
+// input (a.kh = a.kw = 2, a.up2 = 0, a.ho x a.wo = the source size; pad (1 - a, 1 - b); weights of the phase at
+// a.w_bs elements per phase) and stores GEMM row (img, i, j) at output pixel (img, 2i + a, 2j + b) (PixPhase).
+template <int BM, int BN, int WGM, int WGN, int S, int EP, bool GEG = false, bool PH = false>
 __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned bytes0, unsigned bytes1,
                                               unsigned bytesw) {
   constexpr int KB = 64;
@@ -92,6 +96,10 @@ __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned 
   extern __shared__ __attribute__((aligned(16))) char lds[];
   HALO_STAMP(0);
 
+  if constexpr (PH) {  // what the host guarantees for a phase launch, as constants: the unused paths fold away
+    a.kh = 2; a.kw = 2; a.stride = 1; a.up2 = 0; a.c1 = 0; a.splits = 1;
+    a.res = nullptr; a.emb = nullptr; a.ln_rows = nullptr; a.out_f32 = 0; a.out_mode = 0;
+  }
   int kt_begin = 0, kt_end = a.nk;
   if (a.splits > 1) {  // split-K: blockIdx.z = k-range, raw fp32 partial sums into slab z
     const int z = blockIdx.z;
@@ -108,7 +116,16 @@ __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned 
   const int nwg = gridDim.x, orig = blockIdx.x;
   const int xcd = orig & 7, q = nwg >> 3, rr = nwg & 7;
   const int wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
-  const int mt = wgid / tiles_n, nt = wgid - mt * tiles_n;
+  int mt = wgid / tiles_n;
+  const int nt = wgid - mt * tiles_n;
+  int phase = 0;
+  if constexpr (PH) {  // the four phases of an M tile are neighbours on one XCD: they share the input through L2
+    phase = mt & 3;
+    mt >>= 2;
+    a.pad_t = 1 - (phase >> 1);
+    a.pad_l = 1 - (phase & 1);
+    a.weight += (long)phase * a.w_bs * 2;
+  }
   const int m0 = mt * BM, n0 = nt * BN;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -239,6 +256,20 @@ __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned 
   }
 
   HALO_STAMP(2);
+  if constexpr (PH) {
+    const PixPhase pm{a.h, a.w, phase >> 1, phase & 1};
+    if constexpr (TM % EP == 0 && (BM / EP) * (BN + 4) * 4 <= S * STAGE) {
+      if (a.epi_vec && epi_vec_ok(a)) {
+        epilogue_vec<BM, BN, WGM, WGN, NT, EP, RowsFrom, false, PixPhase>(acc, a, m0, n0, wm, wn, lane, tid, lds,
+                                                                          RowsFrom{m0}, pm);
+        HALO_STAMP(3);
+        return;
+      }
+    }
+    epilogue_scalar<TM, TN, WTM, WTN, PixPhase>(acc, a, m0, n0, wm, wn, lane, pm);
+    HALO_STAMP(3);
+    return;
+  }
   if constexpr (TM % EP == 0 && (BM / EP) * (BN + 4) * 4 <= S * STAGE) {
     if ((a.epi_vec || a.out_mode == 2) && epi_vec_ok(a)) {
       if constexpr (GEG) epilogue_geglu<BM, BN, WGM, WGN, NT, EP>(acc, a, m0, n0, wm, wn, lane, tid, lds);
@@ -255,10 +286,10 @@ __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned 
 // hardware admits floor(800 / (ceil(sgpr / 16) * 16 + 16)) waves per SIMD; MI355X_MICROARCH.md
 // "Residency"), so the 16-wave 128x128 tile (64 KB of LDS: two blocks fit) is built with its
 // SGPR budget capped; the others keep the compiler's allocation.
-template <int BM, int BN, int WGM, int WGN, int S, int EP, bool GEG = false>
+template <int BM, int BN, int WGM, int WGN, int S, int EP, bool GEG = false, bool PH = false>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(ConvArgs a, int tiles_n, unsigned bytes0,
                                                                   unsigned bytes1, unsigned bytesw) {
-  conv_dma_body<BM, BN, WGM, WGN, S, EP, GEG>(a, tiles_n, bytes0, bytes1, bytesw);
+  conv_dma_body<BM, BN, WGM, WGN, S, EP, GEG, PH>(a, tiles_n, bytes0, bytes1, bytesw);
 }
 
 template <int BM, int BN, int WGM, int WGN, int S, int EP, bool GEG = false>
@@ -412,6 +443,101 @@ int dma_grouped(const rdeic_conv_desc* d, int tile, hipStream_t s, bool* fused) 
     if (fused) *fused = (i0 == 0 ? f : (*fused && f));
   }
   return RDEIC_OK;  // *fused false if any group could not fuse: the caller recomputes the statistics
+}
+
+// ---- nearest-x2 upsample 3x3 conv as four folded 2x2 phase convs (rdeic_conv2d_up2_phases) ----
+// Output pixel (2i + a, 2j + b) of conv3x3(pad 1)(nearest_x2(x)) is a 2x2 conv of x with the folded weights
+// W_ab = R_a W R_b^T, zero padding (top, left) = (1 - a, 1 - b): 16 tap products per source pixel where the
+// fused gather multiplies 36. One launch covers the four phases (conv_dma_body<PH>).
+namespace {
+template <int BM, int BN, int WGM, int WGN, int S, int EP>
+int launch_dma_ph(ConvArgs a, unsigned b0, unsigned b1, unsigned bw, hipStream_t s, bool* fused) {
+  if (a.gn_part) {
+    const bool ok = (a.h * a.w) % 64 == 0 && stats_tile_ok<BM, BN, WGM, WGM * WGN * 64, EP>() &&
+                    dma_vec_epilogue<BM, BN, WGM, WGN, S, EP>(a);
+    if (!ok) a.gn_part = nullptr;
+    if (fused) *fused = ok;
+  }
+  const int tn = cdiv(a.cout, BN);
+  const long tiles = (long)cdiv(a.M, BM) * 4 * tn;
+  constexpr int lds = S * (BM + BN) * 128;
+  hipLaunchKernelGGL((conv_dma_kernel<BM, BN, WGM, WGN, S, EP, false, true>), dim3((unsigned)tiles),
+                     dim3(WGM * WGN * 64), lds, s, a, tn, b0, b1, bw);
+  return launch_status();
+}
+
+// tiles built for the phase launch: 32 256x256/16, 33 256x128/16, 25 128x128/8, 26 64x128/4 S3, 30 64x128/4 S2,
+// 36 64x128/8; any other id takes the heuristic (the rule of launch_dma_auto over the grid of all four phases)
+int launch_ph_auto(const ConvArgs& a, unsigned b0, unsigned b1, unsigned bw, hipStream_t s, int tile, bool* fused) {
+  if (tile != 32 && tile != 33 && tile != 25 && tile != 26 && tile != 30 && tile != 36) {
+    const long t128 = (long)cdiv(a.M, 128) * cdiv(a.cout, 128) * 4;
+    const long t256 = (long)cdiv(a.M, 256) * cdiv(a.cout, 256) * 4;
+    const float useful256 = (float)a.M * a.cout / ((float)cdiv(a.M, 256) * 256 * cdiv(a.cout, 256) * 256);
+    tile = (t256 >= 256 && useful256 >= 0.9f) ? 32 : t128 >= 256 ? 25 : 26;
+  }
+  switch (tile) {
+    case 32: return launch_dma_ph<256, 256, 4, 4, 2, 4>(a, b0, b1, bw, s, fused);
+    case 33: return launch_dma_ph<256, 128, 4, 4, 2, 2>(a, b0, b1, bw, s, fused);
+    case 25: return launch_dma_ph<128, 128, 2, 4, 2, 2>(a, b0, b1, bw, s, fused);
+    case 30: return launch_dma_ph<64, 128, 2, 2, 2, 2>(a, b0, b1, bw, s, fused);
+    case 36: return launch_dma_ph<64, 128, 2, 4, 2, 2>(a, b0, b1, bw, s, fused);
+    default: return launch_dma_ph<64, 128, 2, 2, 3, 2>(a, b0, b1, bw, s, fused);  // 26
+  }
+}
+}  // namespace
+
+// Images per launch of the phase path: the largest group whose input span and (4x larger) output span both stay
+// below 2 GiB, evened out over the groups; 0 when one image already exceeds that.
+int up2_phase_group(const rdeic_conv_desc* d) {
+  const long ipix = (long)d->h * d->w;
+  const long per_in = ipix * d->ld0 * 2, per_out = 4 * ipix * d->out_ld * 2;
+  const long per = per_in > per_out ? per_in : per_out;
+  const long lim = (1l << 31) - 1;
+  if (d->n <= 0 || per <= 0 || per > lim) return 0;
+  long g = lim / per;
+  if (g > d->n) g = d->n;
+  const long groups = (d->n + g - 1) / g;
+  return (int)((d->n + groups - 1) / groups);
+}
+
+bool up2_phases_ok(const rdeic_conv_desc* d, long phase_stride) {
+  if (!d || !d->in0 || !d->weight || !d->out || d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0) return false;
+  if (d->dtype != 1 || d->out_f32 || !d->up2 || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad_t != 1 ||
+      d->pad_l != 1 || d->ho != 2 * d->h || d->wo != 2 * d->w)
+    return false;
+  if (d->c1 || d->in1 || d->c0 <= 0 || d->c0 % 64 || d->out_mode != 0 || d->batch > 1) return false;
+  if (d->gn_ab || d->emb || d->res || d->ln_rows || d->ln_colsum) return false;
+  if (d->wld != 4 * d->c0 || phase_stride < (long)d->cout * d->wld || phase_stride % 8) return false;
+  if (d->ld0 < d->c0 || d->ld0 % 8 || ((uintptr_t)d->in0 % 16) || ((uintptr_t)d->weight % 16)) return false;
+  if (d->cout % 8 || d->out_ld < d->cout || d->out_ld % 8 || ((uintptr_t)d->out % 16)) return false;
+  if ((long)d->cout * d->wld * 2 >= (1l << 31)) return false;
+  return up2_phase_group(d) > 0;
+}
+
+// -1: not eligible (nothing launched; the caller runs the fused-gather path)
+int launch_up2_phases(const rdeic_conv_desc* d, long phase_stride, int tile, hipStream_t s, bool* fused) {
+  if (!up2_phases_ok(d, phase_stride)) return -1;
+  const int g = up2_phase_group(d);
+  const long ipix = (long)d->h * d->w;
+  const long per_in = ipix * d->ld0 * 2, per_out = 4 * ipix * d->out_ld * 2;
+  rdeic_conv_desc e = *d;  // one phase: the 2x2 conv over the raw input, h x w GEMM rows per image
+  e.up2 = 0; e.kh = 2; e.kw = 2; e.stride = 1; e.pad_t = 1; e.pad_l = 1; e.ho = d->h; e.wo = d->w;
+  for (int i0 = 0; i0 < d->n; i0 += g) {
+    e.n = d->n - i0 < g ? d->n - i0 : g;
+    e.in0 = (const char*)d->in0 + i0 * per_in;
+    e.out = (char*)d->out + i0 * per_out;
+    ConvArgs ea;
+    bool vec = false;
+    unsigned b0, b1, bw;
+    if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return i0 == 0 ? -1 : RDEIC_EINVAL;
+    ea.w_bs = phase_stride;
+    ea.gn_row0 = (int)(i0 * ipix);
+    bool f = false;
+    const int rc = launch_ph_auto(ea, b0, b1, bw, s, tile, &f);
+    if (rc != RDEIC_OK) return rc;
+    if (fused) *fused = (i0 == 0 ? f : (*fused && f));
+  }
+  return RDEIC_OK;
 }
 
 }  // namespace rdeic_conv

@@ -29,6 +29,7 @@ int g_force_tile = -1;  // >= 0: force launch_plain_auto's candidate (rdeic_set_
 int g_dma = 1;          // LDS-DMA path for cin % 64 == 0 (rdeic_set_conv_option(5, v))
 int g_halo = 1;         // 3x3 halo conv: 0 off, 1 for GroupNorm-input convs (default), 2 for every eligible conv
 int g_halo8 = 1;        // the 8-row halo conv where it applies (rdeic_set_conv_option(9, v))
+int g_up2_phases = 1;   // rdeic_conv2d_up2_phases runs the four folded 2x2 phase convs (rdeic_set_conv_option(11, v))
 
 namespace {
 
@@ -786,6 +787,31 @@ extern "C" int rdeic_conv2d_splitk(const rdeic_conv_desc* d, int32_t splits, flo
                          d->out_f32 ? 0 : 1, (hipStream_t)stream);
 }
 
+// The nearest-x2 upsample 3x3 conv as four folded 2x2 phase convs in one LDS-DMA launch (conv_dma.hip). Returns 1
+// and launches nothing when the switch is off or the layer is not eligible.
+extern "C" int rdeic_conv2d_up2_phases(const rdeic_conv_desc* d, int64_t phase_stride, int32_t tile, void* stream) {
+  if (!d) return RDEIC_EINVAL;
+  if (!g_up2_phases || !g_dma || g_conv_path == 0) return 1;
+  if (d->gn_part && (d->gn_hw <= 0 || d->gn_hw % 64 || (long)d->n * d->ho * d->wo % d->gn_hw)) return RDEIC_EINVAL;
+  if (!up2_phases_ok(d, phase_stride)) return 1;
+  bool fused = false;
+  int rc;
+  {
+    // the MACs executed: four 2x2 convs over the source pixels (4/9 of the fused gather's)
+    const double pix = (double)d->n * d->h * d->w;
+    rdeic_prof_add_bytes(2.0 * (pix * d->c0 + 4.0 * d->cout * d->wld + 4.0 * pix * d->cout));
+    ProfScope ps((hipStream_t)stream, RDEIC_PROF_CONV, 2.0 * pix * 4.0 * d->c0 * d->cout * 4.0);
+    rc = launch_up2_phases(d, phase_stride, tile, (hipStream_t)stream, &fused);
+  }
+  if (rc == -1) return RDEIC_EINVAL;  // unreachable: up2_phases_ok covers the launch's conditions
+  if (rc != RDEIC_OK || !d->gn_part || fused) return rc;
+  return gn_rows_partial(d->out, (long)d->n * d->ho * d->wo, d->cout, d->out_ld, d->gn_hw, d->gn_part, 1,
+                         (hipStream_t)stream);
+}
+
+// Images per launch of rdeic_conv2d_up2_phases for this descriptor (host arithmetic only).
+extern "C" int rdeic_conv2d_up2_group(const rdeic_conv_desc* d) { return d ? up2_phase_group(d) : 0; }
+
 extern "C" int rdeic_set_conv_path(int32_t path) {
   int prev = g_conv_path;
   g_conv_path = path;
@@ -805,5 +831,6 @@ extern "C" int rdeic_set_conv_option(int32_t key, int32_t value) {
   if (key == 8) { int prev = rdeic_g_attn512; rdeic_g_attn512 = value; return prev; }
   if (key == 9) { int prev = g_halo8; g_halo8 = value; return prev; }
   if (key == 10) { int prev = g_edge; g_edge = value; return prev; }
+  if (key == 11) { int prev = g_up2_phases; g_up2_phases = value; return prev; }
   return RDEIC_EINVAL;
 }

@@ -92,8 +92,12 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
            act: int = NONE, slope: float = 0.0, res: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, out_f32: bool = False, pixel_shuffle: bool = False,
            geglu: bool = False, stats: bool = False, stats_hw: Optional[int] = None,
-           images: Optional[int] = None, ln_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+           images: Optional[int] = None, ln_rows: Optional[torch.Tensor] = None,
+           phases: Optional[ConvParams] = None) -> torch.Tensor:
     """out = act(conv(cat(x, x2)) + bias + emb) + res   (all NHWC).
+    phases (with up2): the layer's folded 2x2 phase weights (ParamStore.conv_up2_phases); the conv then runs as
+    four phase convs in one launch (4/9 of the MACs) where the library takes it (UP2_PHASES, bf16, no
+    concat / GroupNorm prologue / emb / residual / split-K), else with p through the fused gather.
     images: how many images the launch covers when that is not n (token rows of ops.linear); the
     inference split-K count is chosen per image (SPLITK_NOMINAL_BATCH).
     geglu: p packed by ParamStore.conv_geglu; out = value * gelu(gate), cout/2 channels (bf16).
@@ -218,6 +222,21 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
             if tile >= 0:
                 TILE_TABLE[key] = tile
 
+    if up2 and phases is not None and UP2_PHASES and splits == 1 and x.dtype == torch.bfloat16 and gn is None \
+            and x2 is None and emb is None and res is None and ln_rows is None and d.out_mode == 0 and not d.out_f32 \
+            and (p.kh, p.kw, p.stride, pt, pl) == (3, 3, 1, 1, 1) and (ho, wo) == (2 * h, 2 * w) \
+            and phases.weight.dtype == torch.bfloat16 and phases.cout == p.cout and phases.wld == 4 * c0:
+        dp = ConvDesc.from_buffer_copy(d)
+        dp.weight, dp.wld = phases.weight.data_ptr(), phases.wld
+        key = tile_key(n * h * w, c0, 0, phases, 2, 0, False, False, act, odt)
+        ptile = TILE_TABLE.get(key, -1) if FORCE_TILE is None else FORCE_TILE
+        # the MACs executed: four 2x2 convs over the source pixels
+        ptag = ("conv", 2.0 * n * h * w * 4 * c0 * p.cout * 4,
+                (n, h, w, c0, c1, p.cout, p.kh, p.stride, False, 2, d.out_mode))
+        if _launch_soft(ptag, "rdeic_conv2d_up2_phases", C.byref(dp), phases.weight.stride(0), ptile, stream_ptr()):
+            if part is not None:
+                _attach_gn_part(out, part, d.gn_hw)
+            return out
     tag = ("conv", flops, (n, h, w, c0, c1, p.cout, p.kh, p.stride, gn is not None, int(up2), d.out_mode))
     if splits > 1:
         ws = _splitk_workspace(splits * n * ho * wo * p.cout, x.device)
@@ -260,6 +279,9 @@ def _gn_part_of(t: Optional[torch.Tensor], hw: int):
 # Layers whose channel segments are multiples of 64 run on the LDS-DMA kernel (tile ids 21..38,
 # rdeic_hip.h); the others on the register-staged tiles (0..10).
 AUTOTUNE = False
+# conv2d(up2=True, phases=...) runs the four folded 2x2 phase convs (rdeic_conv2d_up2_phases). The library has
+# the same switch (rdeic_set_conv_option(11, .), set_up2_phases sets both); either one off = the fused gather.
+UP2_PHASES = True
 FORCE_TILE: Optional[int] = None  # tests / tools: run every eligible conv on this tile id
 GEGLU_FUSED = True  # bf16 transformer FF: GEGLU in the projection's epilogue (conv out_mode 2)
 TILE_CANDIDATES = (0, 1, 3, 4, 6, 8, 10)
@@ -270,9 +292,10 @@ TILE_TABLE_PATH = os.environ.get("RDEIC_TILE_TABLE") or os.path.join(os.path.dir
                                                                      "conv_tiles.json")
 
 
-def tile_key(m: int, c0: int, c1: int, p: "ConvParams", up2: bool, out_mode: int, res: bool, emb: bool, act: int,
+def tile_key(m: int, c0: int, c1: int, p: "ConvParams", up2, out_mode: int, res: bool, emb: bool, act: int,
              odt) -> str:
-    """Layer-shape key of the tile table: GEMM M, the concat split, filter, stride, fused epilogue."""
+    """Layer-shape key of the tile table: GEMM M, the concat split, filter, stride, fused epilogue.
+    up2 = 2: the phase launch of an upsample conv (M = source pixels, p = the folded 2x2 weights)."""
     return (f"m{m}:c{c0}+{c1}:o{p.cout}:k{p.kh}x{p.kw}:s{p.stride}:up{int(up2)}:om{out_mode}:"
             f"r{int(res)}:e{int(emb)}:a{act}:{'f32' if odt == torch.float32 else 'bf16'}")
 
@@ -452,6 +475,20 @@ def _launch(tag, name: str, *args):
     record_profile(tag, ev0, ev1)
 
 
+def _launch_soft(tag, name: str, *args) -> bool:
+    """_launch for an entry point that may decline (status 1, nothing launched): False then."""
+    if PROFILE is None:
+        return _lib.call_soft(name, *args, tag=tag)
+    ev0 = torch.cuda.Event(enable_timing=True)
+    ev1 = torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    if not _lib.call_soft(name, *args, tag=tag):
+        return False
+    ev1.record()
+    record_profile(tag, ev0, ev1)
+    return True
+
+
 def record_profile(tag, ev0, ev1):
     kind, work, meta = tag
     if kind == "conv":
@@ -544,7 +581,7 @@ def set_conv_path(path: int) -> int:
 def set_conv_option(key: int, value: int) -> int:
     """rdeic_set_conv_option (include/rdeic_hip.h): 0 vector epilogue, 1 dh=64 attention kernel, 3 swizzle,
     4 forced register tile, 5 LDS-DMA path, 6 halo conv, 8 d=512 attention form, 9 8-row halo conv, 10 VAE edge
-    convs."""
+    convs, 11 the phase launch of the nearest-x2 upsample convs."""
     return int(_lib.load().rdeic_set_conv_option(int(key), int(value)))
 
 
@@ -563,6 +600,15 @@ HALO_MAX_C = 512
 # launch counters of the library (rdeic_launch_count, RDEIC_COUNT_* in include/rdeic_hip.h)
 COUNT_HALO_CONV, COUNT_GN_APPLY, COUNT_LAYERNORM, COUNT_HALO_SMALL, COUNT_LN_FUSED, COUNT_SPLITK, COUNT_EDGE, \
     COUNT_GN_PARTS_APPLY = 0, 1, 2, 3, 4, 5, 6, 7
+
+
+def set_up2_phases(on: bool) -> bool:
+    """Switch the phase launch of the nearest-x2 upsample convs (here and in the library); returns the previous."""
+    global UP2_PHASES
+    prev = UP2_PHASES
+    UP2_PHASES = bool(on)
+    _lib.load().rdeic_set_conv_option(11, int(UP2_PHASES))
+    return prev
 
 
 def launch_count(kind: int) -> int:

@@ -15,6 +15,22 @@ from . import ops
 from . import weights as W
 
 
+def fold_up2_phases(w: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """Folded weights of conv3x3(pad 1)(nearest_x2(x)) as four 2x2 phase convs of x.
+
+    Output pixel (2i + a, 2j + b) is a 2x2 conv of x with W_ab = R_a W R_b^T, R_0 = [[1,0,0],[0,1,1]],
+    R_1 = [[1,1,0],[0,0,1]], zero padding (top, left, bottom, right) = (1 - a, 1 - b, a, b).
+    w: [cout, cin, 3, 3] master weights. Returns [4, cout, 4 * cin] in `dtype`: phase 2a + b, k = (dy, dx)
+    row-major then channel (the library's packed k order); summed in float64 and rounded once."""
+    cout, cin, kh, kw = w.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError("the phase fold is for 3x3 convs")
+    r = torch.tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]], dtype=torch.float64, device=w.device)
+    # f[a, b, co, dy, dx, ci] = sum_{ky, kx} r[a, dy, ky] w[co, ci, ky, kx] r[b, dx, kx]
+    f = torch.einsum("ayk,oikl,bxl->aboyxi", r, w.double(), r)
+    return f.reshape(4, cout, 4 * cin).to(dtype).contiguous()
+
+
 class ParamStore:
     def __init__(self, compute_dtype=torch.bfloat16, device="cuda"):
         self.compute_dtype = compute_dtype
@@ -98,6 +114,24 @@ class ParamStore:
                     b = torch.nn.functional.pad(b, (0, cout_pad - b.shape[0]))
             k = w.shape[-1] if w.dim() == 4 else 1
             p = ops.ConvParams.pack(w, b, stride=stride, pad=(k // 2 if pad is None else pad), dtype=dtype)
+            self._packed[key] = p
+        return p
+
+    def conv_up2_phases(self, prefix: str) -> Optional[ops.ConvParams]:
+        """The 3x3 conv after a nearest-x2 upsample as four folded 2x2 phase convs (fold_up2_phases) for
+        ops.conv2d(up2=True, phases=...): weight [4][cout][4 cin] bf16, folded from the fp32 master in float64
+        and rounded once; the bias is the layer's. None where the phase launch does not apply (fp32 parity
+        mode, cin not a multiple of 64): the caller then runs the fused gather."""
+        w = self.t[prefix + ".weight"]
+        if self.compute_dtype != torch.bfloat16 or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[1] % 64:
+            return None
+        key = (prefix, "up2_phases")
+        p = self._packed.get(key)
+        if p is None:
+            b = self.t.get(prefix + ".bias")
+            f = fold_up2_phases(w).to(torch.bfloat16).contiguous()
+            p = ops.ConvParams(f, 4 * w.shape[1], self.conv(prefix).bias if b is not None else None, w.shape[0],
+                               w.shape[1], 2, 2, 1, 1)
             self._packed[key] = p
         return p
 

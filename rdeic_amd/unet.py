@@ -282,7 +282,7 @@ class UNet:
             elif isinstance(layer, Down):
                 x = ops.conv2d(x, s.conv(layer.prefix, stride=2, pad=1), stats=st)
             elif isinstance(layer, Up):
-                x = ops.conv2d(x, s.conv(layer.prefix), up2=True, stats=st)
+                x = ops.conv2d(x, s.conv(layer.prefix), up2=True, stats=st, phases=s.conv_up2_phases(layer.prefix))
             else:
                 raise TypeError(layer)
         return x

@@ -168,6 +168,6 @@ class AutoencoderKL:
             for blk in lvl:
                 h = self.resnet(blk, h)
             if up is not None:
-                h = ops.conv2d(h, s.conv(up), up2=True, stats=True)
+                h = ops.conv2d(h, s.conv(up), up2=True, stats=True, phases=s.conv_up2_phases(up))
         ab = ops.group_norm_ab(h, s.get(d + "norm_out.weight"), s.get(d + "norm_out.bias"), 32, GN_EPS)
         return ops.conv2d(h, s.conv(d + "conv_out"), gn=ab, gn_silu=True, out_f32=out_f32)
