@@ -45,3 +45,6 @@ $(BUILD)/elementwise.hip.o $(BUILD)/entropy.hip.o: HIPFLAGS += -ffp-contract=off
 # conv kernels: no SLP vectorisation (packed-f32 VALU beside MFMAs is an anti-lever on gfx950,
 # MI355X_MICROARCH.md constants table; measured r04 on the halo conv: -1 to -2% time)
 $(BUILD)/conv_gemm.hip.o $(BUILD)/conv_dma.hip.o $(BUILD)/conv_halo.hip.o $(BUILD)/conv_edge.hip.o: HIPFLAGS += -fno-slp-vectorize
+
+# training flash attention: as attention.hip (the softmax / dS arithmetic reads every MFMA result)
+$(BUILD)/attention_bwd.hip.o: HIPFLAGS += -mllvm -amdgpu-mfma-vgpr-form=1

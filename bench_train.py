@@ -44,6 +44,8 @@ def parse(argv=None):
                     help="split counts of the step's >= 32 k-tile convs (A/B; ops.SPLITK_TRAIN)")
     ap.add_argument("--ft-splitk", default="short", choices=["short", "long", "off"],
                     help="split-K policy of the step's convs (A/B; finetune.FT_SPLITK)")
+    ap.add_argument("--train-attn", default=None, choices=["auto", "flash", "materialized"],
+                    help="attention of the step (A/B; autograd.set_attention_impl; default: the library's)")
     ap.add_argument("--eager", action="store_true",
                     help="eager steps (default on one GPU: the step captured once as a hipGraph and replayed)")
     return ap.parse_args(argv)
@@ -57,6 +59,9 @@ def main(argv=None):
     from rdeic_amd import finetune
     from rdeic_amd.finetune import CapturedStep, FineTuner, nchw_draws_to_nhwc
     finetune.FT_SPLITK = args.ft_splitk
+    from rdeic_amd import autograd
+    if args.train_attn:
+        autograd.set_attention_impl(args.train_attn)
     for kv in args.conv_option:
         k, v = kv.split("=")
         ops.set_conv_option(int(k), int(v))
@@ -132,7 +137,7 @@ def main(argv=None):
         pr = ops.prof_read()
         peak = PEAK[args.dtype]
         fam = {}
-        for kind in ("conv", "gemm", "gn_apply"):
+        for kind in ("conv", "gemm", "attention", "attention_dh16", "gn_apply"):
             if kind in pr:
                 n, work, kms = pr[kind]
                 fam[kind] = {"launches": n, "ms": round(kms, 3),
@@ -140,11 +145,12 @@ def main(argv=None):
                                  round(work / (kms * 1e-3) / (1e12 if kind != "gn_apply" else 1e9), 2)}
         conv = pr.get("conv")
         gemm = pr.get("gemm")
-        fl = (conv[1] if conv else 0.0) + (gemm[1] if gemm else 0.0)
-        kms = (conv[2] if conv else 0.0) + (gemm[2] if gemm else 0.0)
+        attn = [pr[kind] for kind in ("attention", "attention_dh16") if kind in pr]  # the flash path's launches
+        fl = (conv[1] if conv else 0.0) + (gemm[1] if gemm else 0.0) + sum(a[1] for a in attn)
+        kms = (conv[2] if conv else 0.0) + (gemm[2] if gemm else 0.0) + sum(a[2] for a in attn)
         achieved = fl / (kms * 1e-3) / 1e12 if kms else 0.0
         roof = {"bound": "mfma", "kernel": "conv (forward / input-gradient implicit GEMM) + strided GEMM (weight "
-                "gradients, attention)", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                "gradients, materialised attention) + flash attention", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
                 "frac": round(achieved / peak, 4), "traffic": None, "flops_per_step": fl,
                 "kernel_ms_per_step": round(kms, 3), "step_wall_ms_profiled": round(1000 * wall, 2),
                 "families": fam}
@@ -166,6 +172,8 @@ def main(argv=None):
                                    "UNet and VAE frozen), AdamW lr 2e-5",
                        "global_batch": world * B, "image_size": S, "parallelism": f"dp{world}",
                        "trainable_params": ft.num_params(), "steps_per_s": round(args.steps / elapsed, 4),
+                       "train_attention": autograd.get_attention_impl(),
+                       "peak_mem_mb": round(torch.cuda.max_memory_allocated(dev) / 2**20, 1),
                        "execution": "hipGraph replay of the captured step" if graph is not None else "eager",
                        "mean_loss": round(sum(loss_vals) / len(loss_vals), 5)},
             "roofline": roof,

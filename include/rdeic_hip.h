@@ -484,6 +484,24 @@ int rdeic_layernorm_bwd_res(const void* x, int32_t ldx, int64_t rows, int32_t c,
 /* ds = p * (dp - rowsum(p * dp)) * scale  (p [rows][cols] of rdeic_softmax_rows, dp fp32) */
 int rdeic_softmax_bwd_rows(const void* p, const float* dp, int64_t rows, int32_t cols, float scale, void* ds,
                            int32_t dtype, void* stream);
+/* Flash attention for training (bf16 only: dtype 1; dh 16 or 64; 'b n (h d)' token tensors with row
+ * strides; no [lq][lk] tensor in memory). Inputs: 16-byte aligned, strides a multiple of 8 elements;
+ * outputs: 8-byte aligned, strides a multiple of 4. Counted under RDEIC_PROF_ATTN / _ATTN_SMALL.
+ *   fwd_lse: o = softmax(q k^T scale) v and lse[b][h][i] = ln sum_j exp(scale q_i . k_j) (fp32)
+ *   bwd:     from q, k, v, o, d_o and that lse: dq = dS k, dk = dS^T q, dv = P^T d_o with
+ *            P = exp(scale S - lse), dS = P (d_o v^T - rowsum(d_o o)) scale. dq may be null, and so may
+ *            the pair dk / dv (not computed then). Two sweeps (per key block, per query block) and
+ *            fixed-order fp32 slab sums: no atomics, bit-reproducible. ws: 16-byte aligned, at least
+ *            bwd_workspace bytes (pure host query, monotone in lq). */
+int rdeic_attention_fwd_lse(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv,
+                            void* o, int32_t ldo, float* lse, int32_t batch, int32_t heads, int32_t lq, int32_t lk,
+                            int32_t dh, float scale, int32_t dtype, void* stream);
+size_t rdeic_attention_bwd_workspace(int32_t batch, int32_t heads, int32_t lq, int32_t lk, int32_t dh);
+int rdeic_attention_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv,
+                        const void* o, int32_t ldo, const void* d_o, int32_t lddo, const float* lse,
+                        void* dq, int32_t lddq, void* dk, int32_t lddk, void* dv, int32_t lddv,
+                        void* ws, size_t ws_bytes, int32_t batch, int32_t heads, int32_t lq, int32_t lk,
+                        int32_t dh, float scale, int32_t dtype, void* stream);
 /* GEGLU backward: x = [value | gate] [rows][2c], dy [rows][c] -> dx [rows][2c] */
 int rdeic_geglu_bwd(const void* x, int32_t ldx, int64_t rows, int32_t c, const void* dy, int32_t ldy, void* dx,
                     int32_t lddx, int32_t dtype, void* stream);

@@ -164,6 +164,11 @@ PROTOTYPES = {
     "rdeic_layernorm_bwd_res": (C.c_int, [_p, _i32, _i64, _i32, _p, _f, _p, _i32, _p, _i32, _p, _i32, _p, _p, _i32, _p,
                                           _sz, _i32, _p]),
     "rdeic_softmax_bwd_rows": (C.c_int, [_p, _p, _i64, _i32, _f, _p, _i32, _p]),
+    "rdeic_attention_fwd_lse": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _f,
+                                          _i32, _p]),
+    "rdeic_attention_bwd_workspace": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "rdeic_attention_bwd": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _i32, _p, _i32, _p,
+                                      _i32, _p, _sz, _i32, _i32, _i32, _i32, _i32, _f, _i32, _p]),
     "rdeic_geglu_bwd": (C.c_int, [_p, _i32, _i64, _i32, _p, _i32, _p, _i32, _i32, _p]),
     "rdeic_ckbd_train_anchor": (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p]),
     "rdeic_ckbd_mask": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p]),

@@ -13,13 +13,17 @@ Backward formulations (reference modules whose autograd they replace are cited p
          dY zero-inserted; nearest-up input: 2x2 sum of the result); dW = split-K GEMM dY^T . im2col(X);
          db / d(timestep emb) = column sums of dY
   norms  GroupNorm(+SiLU) / LayerNorm closed-form backward with the saved / recomputed statistics
-  attn   materialised softmax(QK^T s) V: dP = dO V^T, dS = P (dP - rowsum(P dP)) s, dQ = dS K,
-         dK = dS^T Q, dV = P^T dO, all strided batched MFMA GEMMs over (image, head)
+  attn   softmax(QK^T s) V with dP = dO V^T, dS = P (dP - rowsum(P dP)) s, dQ = dS K, dK = dS^T Q,
+         dV = P^T dO. bf16 with head dim 16 / 64: flash kernels (attention_bwd.hip) that keep only O and
+         the row log-sum-exp and recompute P in the backward; otherwise (fp32 parity mode, other head
+         dims, or set_attention_impl("materialized")) P is kept and every product is a strided batched
+         MFMA GEMM over (image, head)
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -652,9 +656,52 @@ def _heads_gemm(a, a_sm: int, a_sk: int, a_bs, b, b_sk: int, b_sn: int, b_bs, *,
     return out
 
 
+# Which attention the fine-tune step runs (bench_train.py --train-attn, train.py --attention, env
+# RDEIC_TRAIN_ATTN): "flash" = the LSE forward / recomputing backward of attention_bwd.hip (raises where
+# it cannot run: fp32, head dims other than 16 / 64), "materialized" = P kept, strided GEMMs, "auto" =
+# flash wherever it is eligible, the materialised path otherwise: the default (flash won every pair of the
+# same-box step A/B and every config 5 shape of the micro A/B).
+ATTENTION_IMPLS = ("auto", "flash", "materialized")
+_attention_impl = os.environ.get("RDEIC_TRAIN_ATTN", "auto")
+if _attention_impl not in ATTENTION_IMPLS:
+    raise ValueError(f"RDEIC_TRAIN_ATTN must be one of {ATTENTION_IMPLS}, got {_attention_impl!r}")
+
+
+def set_attention_impl(impl: str) -> None:
+    global _attention_impl
+    if impl not in ATTENTION_IMPLS:
+        raise ValueError(f"attention impl must be one of {ATTENTION_IMPLS}, got {impl!r}")
+    _attention_impl = impl
+
+
+def get_attention_impl() -> str:
+    return _attention_impl
+
+
+def _flash_eligible(q, k, v, heads: int) -> bool:
+    """bf16, head dim 16 / 64, and the entries' layout rules (16-byte aligned rows of contiguous channels)."""
+    return (q.dtype == torch.bfloat16 and k.dtype == q.dtype and v.dtype == q.dtype and q.shape[1] % heads == 0
+            and q.shape[1] // heads in (16, 64)
+            and all(t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0 for t in (q, k, v)))
+
+
+def _use_flash(q, k, v, batch: int, heads: int) -> bool:
+    if _attention_impl == "materialized":
+        return False
+    ok = _flash_eligible(q, k, v, heads)
+    if _attention_impl == "flash":
+        if not ok:
+            raise ValueError(f"flash attention needs bf16, head dim 16 or 64 and 16-byte aligned rows, got {q.dtype} "
+                             f"with {q.shape[1]} channels over {heads} heads, row strides "
+                             f"{q.stride(0)}/{k.stride(0)}/{v.stride(0)}")
+        return True
+    return ok
+
+
 class AttentionFn(torch.autograd.Function):
     """softmax(Q K^T * scale) V per (image, head) over 'b n (h d)' token tensors (CrossAttention.forward,
-    attention.py:171-203), materialised: P is kept for the backward."""
+    attention.py:171-203). Flash path: O and the row log-sum-exp are kept and P is recomputed in the
+    backward; materialised path: P is kept for the backward."""
 
     @staticmethod
     def forward(ctx, q, k, v, batch: int, heads: int, scale: float):
@@ -662,6 +709,16 @@ class AttentionFn(torch.autograd.Function):
         Lk = k.shape[0] // batch
         dh = q.shape[1] // heads
         dev, dt = q.device, q.dtype
+        ctx.flash = _use_flash(q, k, v, batch, heads)
+        if ctx.flash:
+            o = torch.empty((batch * Lq, heads * dh), dtype=dt, device=dev)
+            lse = torch.empty((batch, heads, Lq), dtype=torch.float32, device=dev)
+            call("rdeic_attention_fwd_lse", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                 v.stride(0), o.data_ptr(), o.stride(0), lse.data_ptr(), batch, heads, Lq, Lk, dh, float(scale), _dt(q),
+                 _sp())
+            ctx.dims = (batch, heads, Lq, Lk, dh, scale)
+            ctx.save_for_backward(q, k, v, o, lse)
+            return o
         s = torch.empty((batch, heads, Lq, Lk), dtype=torch.float32, device=dev)
         ldq, ldk, ldv = q.stride(0), k.stride(0), v.stride(0)
         gemm(q, 0, ldq, 1, k, 0, 1, ldk, s, 0, Lk, m=Lq, n=Lk, k=dh, batch=batch * heads, nb2=heads,
@@ -677,6 +734,8 @@ class AttentionFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
+        if ctx.flash:
+            return AttentionFn._flash_backward(ctx, do)
         q, k, v, p = ctx.saved_tensors
         batch, heads, Lq, Lk, dh, scale = ctx.dims
         do = do.contiguous()
@@ -702,6 +761,30 @@ class AttentionFn(torch.autograd.Function):
             dv = _heads_gemm(p, 1, Lk, pl, do, ldo, 1, (Lq * ldo, dh), m=Lk, n=dh, k=Lq, batch=batch, heads=heads,
                              dt=dt, dev=dev)
         return dq, dk, dv, None, None, None
+
+    @staticmethod
+    def _flash_backward(ctx, do):
+        q, k, v, o, lse = ctx.saved_tensors
+        batch, heads, Lq, Lk, dh, scale = ctx.dims
+        do = do.contiguous()
+        dev, dt = q.device, q.dtype
+        c = heads * dh
+        dq = torch.empty((batch * Lq, c), dtype=dt, device=dev) if ctx.needs_input_grad[0] else None
+        dk = dv = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:  # the kernel computes dK and dV as a pair
+            dk = torch.empty((batch * Lk, c), dtype=dt, device=dev)
+            dv = torch.empty((batch * Lk, c), dtype=dt, device=dev)
+        if dq is None and dk is None:
+            return None, None, None, None, None, None
+        nws = int(_lib.load().rdeic_attention_bwd_workspace(batch, heads, Lq, Lk, dh))
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        call("rdeic_attention_bwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+             o.data_ptr(), o.stride(0), do.data_ptr(), do.stride(0), lse.data_ptr(),
+             None if dq is None else dq.data_ptr(), c, None if dk is None else dk.data_ptr(), c,
+             None if dv is None else dv.data_ptr(), c, ws.data_ptr(), nws, batch, heads, Lq, Lk, dh, float(scale),
+             _dt(q), _sp())
+        return (dq, dk if ctx.needs_input_grad[1] else None, dv if ctx.needs_input_grad[2] else None, None, None,
+                None)
 
 
 def attention(q, k, v, batch: int, heads: int, scale: float):

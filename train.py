@@ -69,10 +69,14 @@ def main(argv=None):
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "finetune_ood.yaml"))
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture of the step (one GPU)")
+    ap.add_argument("--attention", default=None, choices=["auto", "flash", "materialized"],
+                    help="attention of the step (autograd.set_attention_impl; default: the library's)")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         cfg = yaml.safe_load(f)
-    from rdeic_amd import parallel
+    from rdeic_amd import autograd, parallel
+    if args.attention:
+        autograd.set_attention_impl(args.attention)
     from rdeic_amd.finetune import CapturedStep, FineTuneConfig, FineTuner, nchw_draws_to_nhwc
     from rdeic_amd.rdeic import RDEIC
     from rdeic_amd.synthetic import synth_context, synth_image, train_draws
