@@ -289,6 +289,25 @@ size_t rdeic_image_ssim_ws_floats(int32_t n, int32_t h, int32_t w, int32_t level
 int rdeic_image_ssim(const uint8_t* a, const uint8_t* b, int32_t n, int32_t h, int32_t w, int32_t levels, float* ws,
                      size_t ws_floats, float* out, void* stream);
 
+/* ------------------------------------------------------------ LPIPS (lpips.hip)
+ * The kernels around the fp32 backbone convs of the LPIPS metric (reference model/lpips.py; network table and
+ * weights: rdeic_amd/lpips.py). All activations fp32 NHWC with a pixel stride; every offset is 64-bit.
+ * prep: uint8 RGB [n][h][w][3] -> fp32 [n][h][w][4] (16-byte aligned); channels 0..2 are the ScalingLayer for
+ * inputs in [0, 1], (((v / 255) * 2 - 1) - shift_c) / scale_c in that order in fp32, channel 3 is zero. */
+int rdeic_lpips_prep(const uint8_t* img, int32_t n, int32_t h, int32_t w, float* out, void* stream);
+/* max pool, window k, stride s, no padding, floor mode: out [n][(h-k)/s+1][(w-k)/s+1][c] (bit-exact) */
+int rdeic_maxpool2d(const float* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ld_in, int32_t k,
+                    int32_t s, float* out, int32_t ld_out, void* stream);
+/* LPIPS distance of one tap: f0, f1 [n][hw][c] (c a multiple of 64, at most 512), lin[c];
+ * out[img] (+= when accumulate) mean_p sum_c lin_c (f0_pc / (|f0_p| + 1e-10) - f1_pc / (|f1_p| + 1e-10))^2.
+ * An all-zero feature vector contributes 0. Per-block partials go to ws (rdeic_lpips_layer_ws_floats(n, hw, c)
+ * floats) and are added in a fixed order in fp64; an image's partial grid depends on (hw, c) only, so its
+ * score is the same in any batch and repeats bit for bit. */
+size_t rdeic_lpips_layer_ws_floats(int32_t n, int64_t hw, int32_t c);
+int rdeic_lpips_layer(const float* f0, int32_t ld0, const float* f1, int32_t ld1, const float* lin, int32_t n,
+                      int64_t hw, int32_t c, int32_t accumulate, float* ws, size_t ws_floats, float* out,
+                      void* stream);
+
 /* ------------------------------------------------------------ host coders
  * Gaussian-conditional tables (compressai 1.2.4 GaussianConditional.update, precision 16).
  * pmf: [levels][pmf_ld] float32 pmf rows of length pmf_len[i] followed by the tail mass

@@ -4,6 +4,7 @@
     python inference_partition.py --input DIR --output DIR [--batch_size 8] [--micro_batch_size 4]
         [--steps 2] [--sampler ddpm|ddim] [--bf16 | --fp16] [--enable_resize_guard --max_long_side 1024
         --upsample_to_original] [--save_intermediates] [--max_images N]
+        [--lpips_backbone PATH [--lpips_lin PATH] [--lpips_net alex|vgg]]
 
 What it keeps from the reference:
   * images are grouped by their padded (multiple-of-64) working size after the optional resize
@@ -24,8 +25,11 @@ What differs, all forced by the offline image or by design:
   * --bf16 selects the bf16 compute path; the default is the fp32 parity path. The reference's
     --fp16 (autocast float16) is accepted and selects the same bf16 path with a notice on stderr:
     no float16 kernels are built for MI355X;
-  * LPIPS needs an AlexNet backbone that is not available offline: the column is NaN; PSNR, SSIM
-    and MS-SSIM are computed on the device (rdeic_amd/metrics.py);
+  * PSNR, SSIM and MS-SSIM are computed on the device (rdeic_amd/metrics.py), and so is LPIPS
+    (rdeic_amd/lpips.py; the reference's pyiqa "lpips": AlexNet, v0.1, inputs in [0, 1]) when
+    --lpips_backbone names a torchvision AlexNet / VGG16 state dict (or the lpips package's full one);
+    the `lin` heads come from --lpips_lin (default ./weight/lpips/<net>.pth, the reference's location).
+    No backbone weights ship with the project: without --lpips_backbone the column is NaN;
   * noise comes from a CPU generator seeded per image (--seed + the image's index in sorted
     order), so results do not depend on how images are grouped into batches and micro-batches.
 """
@@ -146,9 +150,11 @@ def _save_intermediates(model, prefix: str, c_lat: torch.Tensor, hint: torch.Ten
     Image.fromarray(dec[0]).save(f"{prefix}_compressed.png")
 
 
-def compute_metrics(pred: np.ndarray, target: np.ndarray) -> Dict[str, float]:
-    """reference inference_partition.py:28-70 (pyiqa psnr / ssim / ms_ssim / lpips), on the device."""
+def compute_metrics(pred: np.ndarray, target: np.ndarray, lpips_model=None) -> Dict[str, float]:
+    """reference inference_partition.py:28-70 (pyiqa psnr / ssim / ms_ssim / lpips), on the device.
+    lpips_model: an rdeic_amd.lpips.LPIPS, or None (the column stays NaN)."""
     from rdeic_amd import metrics
+    from rdeic_amd.lpips import MIN_SIZE
     p = torch.from_numpy(np.ascontiguousarray(pred[None])).cuda()
     t = torch.from_numpy(np.ascontiguousarray(target[None])).cuda()
     out = {"psnr": float(metrics.psnr(p, t)[0]), "ssim": float("nan"), "ms_ssim": float("nan"),
@@ -158,6 +164,8 @@ def compute_metrics(pred: np.ndarray, target: np.ndarray) -> Dict[str, float]:
         out.update(ssim=float(s[0]), ms_ssim=float(ms[0]))
     elif min(pred.shape[:2]) >= 11:
         out.update(ssim=float(metrics.ssim_levels(p, t, 1)[0, 0, 0]))
+    if lpips_model is not None and min(pred.shape[:2]) >= MIN_SIZE[lpips_model.net]:
+        out.update(lpips=float(metrics.lpips(p, t, lpips_model)[0]))
     return out
 
 
@@ -189,7 +197,18 @@ def parse_args(argv=None) -> Namespace:
     p.add_argument("--upsample_to_original", action="store_true")
     p.add_argument("--upsample_method", type=str, default="lanczos", choices=list(RESAMPLE))
     p.add_argument("--suppress_warnings", action="store_true")
+    p.add_argument("--lpips_backbone", type=str, default="",
+                   help="torchvision AlexNet / VGG16 state dict (or the lpips package's); empty = lpips column NaN")
+    p.add_argument("--lpips_lin", type=str, default="",
+                   help="the LPIPS lin heads (.pth as the reference's, or .npz); default ./weight/lpips/<net>.pth")
+    p.add_argument("--lpips_net", type=str, default="alex", choices=["alex", "vgg"])
     args = p.parse_args(argv)
+    if args.lpips_backbone:  # refused at start-up, not a NaN column at the end
+        if not args.lpips_lin:
+            args.lpips_lin = os.path.join(".", "weight", "lpips", f"{args.lpips_net}.pth")
+        for what, path in (("--lpips_backbone", args.lpips_backbone), ("--lpips_lin", args.lpips_lin)):
+            if not os.path.isfile(path):
+                p.error(f"{what} {path} is not a file")
     if args.fp16:
         print("[inference_partition] --fp16: the reduced-precision path computes in bf16 on MI355X "
               "(float16 autocast is not provided); same as --bf16", file=sys.stderr)
@@ -223,6 +242,10 @@ def main(argv=None) -> List[Dict]:
     if args.suppress_warnings:
         import warnings
         warnings.filterwarnings("ignore")
+    lpips_model = None
+    if args.lpips_backbone:
+        from rdeic_amd.lpips import LPIPS
+        lpips_model = LPIPS(args.lpips_net, backbone=args.lpips_backbone, lin=args.lpips_lin)
     model = _load(args)
     ctx = synth_context().to(model.device)
     os.makedirs(args.output, exist_ok=True)
@@ -277,7 +300,7 @@ def main(argv=None) -> List[Dict]:
                 if up:
                     out = out.resize((m["orig_w"], m["orig_h"]), resample)
                 out.save(f"{prefix}.png")
-                vals = compute_metrics(np.array(out), orig if up else scaled)
+                vals = compute_metrics(np.array(out), orig if up else scaled, lpips_model)
                 records.append({"image": rel, "bpp": bpp, "scale": m["scale"], **vals})
                 bpps.append(bpp)
                 print(f"save to {prefix}.png, bpp {bpp:.3f}, PSNR {vals['psnr']:.2f}dB, SSIM {vals['ssim']:.4f}, "

@@ -1,0 +1,263 @@
+"""LPIPS (Zhang et al. 2018, v0.1; reference model/lpips.py) on the device.
+
+The reference's evaluation reports LPIPS through pyiqa's default metric: AlexNet, v0.1, inputs in [0, 1].
+Here the metric is a table-driven feature extractor over the library's fp32 convs (rdeic_conv2d, ReLU in the
+epilogue as leaky-ReLU with slope 0) plus three kernels of lpips.hip: the ScalingLayer prep (uint8 -> fp32
+NHWC with a zero fourth channel), the max pool, and the per-tap distance (normalise, squared difference,
+`lin` 1x1 conv and spatial mean in one pass).
+
+No backbone weights ship with the project: the caller passes the torchvision AlexNet / VGG16 state dict
+(``features.<i>.weight``) or the `lpips` package's full state dict (``net.slice<k>.<i>.weight``), and the five
+learned `lin` heads in the reference's layout (``lin<k>.model.1.weight``, weight/lpips/<net>.pth) or as an
+.npz. The computation is pinned against an fp64 restatement of model/lpips.py with a seeded random backbone
+and the published heads (tests/lpips_ref.py); parity with pyiqa / the lpips package / torchvision weights is
+unpinned, none of them is available offline.
+
+Scores are batch-invariant bit for bit: split-K is pinned off for the backbone convs, every conv output
+element is one fixed-order k sum, and the distance kernel's partial grid depends on the tap shape only. The
+batch is therefore chunked freely (chunk_pairs) to keep every activation tensor under 2^31 bytes.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, List, Optional, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+# (torchvision `features` index, cout, kernel, stride, pad) / ("pool", k, s) / ("tap",) in forward order.
+# The lpips package's slice<k> holds the modules between tap k-1 and tap k under their features index.
+_ALEX = (("conv", 0, 64, 11, 4, 2), ("tap",), ("pool", 3, 2), ("conv", 3, 192, 5, 1, 2), ("tap",), ("pool", 3, 2),
+         ("conv", 6, 384, 3, 1, 1), ("tap",), ("conv", 8, 256, 3, 1, 1), ("tap",), ("conv", 10, 256, 3, 1, 1),
+         ("tap",))
+_VGG = (("conv", 0, 64, 3, 1, 1), ("conv", 2, 64, 3, 1, 1), ("tap",), ("pool", 2, 2),
+        ("conv", 5, 128, 3, 1, 1), ("conv", 7, 128, 3, 1, 1), ("tap",), ("pool", 2, 2),
+        ("conv", 10, 256, 3, 1, 1), ("conv", 12, 256, 3, 1, 1), ("conv", 14, 256, 3, 1, 1), ("tap",), ("pool", 2, 2),
+        ("conv", 17, 512, 3, 1, 1), ("conv", 19, 512, 3, 1, 1), ("conv", 21, 512, 3, 1, 1), ("tap",), ("pool", 2, 2),
+        ("conv", 24, 512, 3, 1, 1), ("conv", 26, 512, 3, 1, 1), ("conv", 28, 512, 3, 1, 1), ("tap",))
+NETS = {"alex": _ALEX, "vgg": _VGG}
+CHANNELS = {"alex": (64, 192, 384, 256, 256), "vgg": (64, 128, 256, 512, 512)}
+MIN_SIZE = {"alex": 31, "vgg": 16}  # the smallest H, W at which every tap has at least one pixel
+MAX_TENSOR_BYTES = 2 ** 31
+
+
+def _table(net: str):
+    if net not in NETS:
+        raise ValueError(f"unknown LPIPS net {net!r} (alex | vgg)")
+    return NETS[net]
+
+
+def conv_layers(net: str) -> List[Tuple[int, int, int, int, int, int, int]]:
+    """(features index, slice number, cin, cout, kernel, stride, pad) of every conv, in order."""
+    out, cin, k = [], 3, 1
+    for op in _table(net):
+        if op[0] == "conv":
+            out.append((op[1], k, cin, op[2], op[3], op[4], op[5]))
+            cin = op[2]
+        elif op[0] == "tap":
+            k += 1
+    return out
+
+
+def activation_shapes(net: str, h: int, w: int) -> List[Tuple[int, int, int]]:
+    """(h, w, c) of every activation tensor of one image, the 4-channel prep output first.
+    Raises ValueError below the minimum size."""
+    table = _table(net)
+    if h < MIN_SIZE[net] or w < MIN_SIZE[net]:
+        raise ValueError(f"LPIPS({net}) needs H, W >= {MIN_SIZE[net]}, got {h}x{w}")
+    shapes, c = [(h, w, 4)], 4
+    for op in table:
+        if op[0] == "conv":
+            _, _, c, k, s, p = op
+            h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+        elif op[0] == "pool":
+            _, k, s = op
+            h, w = (h - k) // s + 1, (w - k) // s + 1
+        else:
+            continue
+        shapes.append((h, w, c))
+    return shapes
+
+
+def tap_shapes(net: str, h: int, w: int) -> List[Tuple[int, int, int]]:
+    """(h, w, c) of the five taps."""
+    acts, taps, i = activation_shapes(net, h, w), [], 0
+    for op in _table(net):
+        if op[0] == "tap":
+            taps.append(acts[i])
+        else:
+            i += 1
+    return taps
+
+
+def image_bytes(net: str, h: int, w: int) -> int:
+    """fp32 bytes of the largest activation tensor of one image."""
+    return max(4 * a * b * c for a, b, c in activation_shapes(net, h, w))
+
+
+def chunk_pairs(net: str, h: int, w: int) -> int:
+    """Image pairs per backbone launch, a function of (net, H, W) alone: the most for which every activation
+    of the 2 x pairs images stays under 2^31 bytes, at least 1. At 1 the two images of the pair may still be
+    too large together; __call__ then runs prediction and target through the backbone one after the other
+    (split_pair). An image whose own activations reach 2^31 bytes is refused."""
+    per = image_bytes(net, h, w)
+    if per >= MAX_TENSOR_BYTES:
+        raise ValueError(f"LPIPS({net}) at {h}x{w}: one image's activation reaches 2^31 bytes")
+    return max(1, ((MAX_TENSOR_BYTES - 1) // per) // 2)
+
+
+def split_pair(net: str, h: int, w: int) -> bool:
+    """True where even one pair's activations would reach 2^31 bytes in one launch."""
+    return 2 * image_bytes(net, h, w) >= MAX_TENSOR_BYTES
+
+
+def _load_file(path: str) -> Dict[str, torch.Tensor]:
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"LPIPS weights not found: {path}")
+    if path.endswith(".npz"):
+        with np.load(path) as z:
+            return {k: torch.from_numpy(np.array(z[k])) for k in z.files}
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    return sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+
+
+def load_backbone(net: str, src: Union[str, Dict[str, torch.Tensor]]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """[(weight [cout,cin,k,k], bias [cout])] fp32 CPU tensors of every conv, in order, from the torchvision
+    state dict (features.<i>.*) or the lpips package's (net.slice<k>.<i>.*)."""
+    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    layers = conv_layers(net)
+    layouts = ([f"features.{i}" for i, *_ in layers], [f"net.slice{k}.{i}" for i, k, *_ in layers])
+    for names in layouts:
+        if all(f"{n}.weight" in sd and f"{n}.bias" in sd for n in names):
+            break
+    else:
+        raise ValueError(f"LPIPS({net}) backbone: expected the torchvision keys {layouts[0][0]}.weight/.bias ... "
+                         f"{layouts[0][-1]}.weight/.bias or the lpips package's {layouts[1][0]}.weight/.bias ... "
+                         f"{layouts[1][-1]}.weight/.bias; got {sorted(sd)[:6]}{' ...' if len(sd) > 6 else ''}")
+    out = []
+    for name, (_, _, cin, cout, k, _, _) in zip(names, layers):
+        wt = sd[f"{name}.weight"].detach().to("cpu", torch.float32)
+        b = sd[f"{name}.bias"].detach().to("cpu", torch.float32)
+        if tuple(wt.shape) != (cout, cin, k, k) or tuple(b.shape) != (cout,):
+            raise ValueError(f"{name}: shapes {tuple(wt.shape)} / {tuple(b.shape)}, expected "
+                             f"{(cout, cin, k, k)} / {(cout,)}")
+        out.append((wt.contiguous(), b.contiguous()))
+    return out
+
+
+def load_lin(net: str, src: Union[str, Dict[str, torch.Tensor]]) -> List[torch.Tensor]:
+    """The five head vectors [C_k] fp32 (CPU): the reference's .pth layout (lin<k>.model.1.weight [1,C,1,1]),
+    or an .npz / dict with lin0..lin4 (or <net>_lin0..<net>_lin4, the layout of tests/golden/lpips_lin.npz)."""
+    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    out = []
+    _table(net)
+    for k, c in enumerate(CHANNELS[net]):
+        names = (f"lin{k}.model.1.weight", f"{net}_lin{k}", f"lin{k}")
+        v = next((sd[n] for n in names if n in sd), None)
+        if v is None:
+            raise ValueError(f"LPIPS({net}) heads: none of {names} found; got {sorted(sd)[:6]}")
+        v = torch.as_tensor(v).detach().to("cpu", torch.float32).reshape(-1).contiguous()
+        if v.numel() != c:
+            raise ValueError(f"LPIPS({net}) lin{k}: {v.numel()} weights, expected {c}")
+        out.append(v)
+    return out
+
+
+class LPIPS:
+    """LPIPS(net)(pred_u8, target_u8): uint8 [N, H, W, 3] device tensors -> float64 numpy [N]."""
+
+    def __init__(self, net: str = "alex", backbone=None, lin=None, device="cuda"):
+        if backbone is None or lin is None:
+            raise ValueError("LPIPS needs a backbone (torchvision / lpips state dict) and the lin heads; "
+                             "no backbone weights ship with the project")
+        self.net = net
+        self.device = torch.device(device)
+        self.table = _table(net)
+        self.convs = []
+        for i, (wt, b) in enumerate(load_backbone(net, backbone)):
+            if i == 0:  # zero fourth input channel (the prep kernel's): exact zero products, 16-byte gathers
+                wt = torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, 1))
+            _, _, _, _, _, s, p = conv_layers(net)[i]
+            self.convs.append(ops.ConvParams.pack(wt, b, stride=s, pad=p, dtype=torch.float32))
+        self.lin = [v.to(self.device) for v in load_lin(net, lin)]
+
+    # ------------------------------------------------------------------ pieces
+    def prep(self, img_u8: torch.Tensor) -> torch.Tensor:
+        n, h, w, _ = img_u8.shape
+        x = torch.empty((n, h, w, 4), dtype=torch.float32, device=img_u8.device)
+        ops.call("rdeic_lpips_prep", img_u8.contiguous().data_ptr(), n, h, w, x.data_ptr(), ops.stream_ptr())
+        return x
+
+    def features(self, img_u8: torch.Tensor) -> List[torch.Tensor]:
+        """The five taps [n, h_k, w_k, C_k] fp32 of uint8 [n, H, W, 3] images."""
+        x, taps, ci = self.prep(img_u8), [], 0
+        with ops.splitk_as((False, False)):  # a k grouping that depended on the batch would break invariance
+            for op in self.table:
+                if op[0] == "conv":
+                    x = ops.conv2d(x, self.convs[ci], act=ops.LEAKY, slope=0.0)
+                    ci += 1
+                elif op[0] == "pool":
+                    x = max_pool(x, op[1], op[2])
+                else:
+                    taps.append(x)
+        return taps
+
+    def _chunk(self, pred: torch.Tensor, tgt: torch.Tensor, out: torch.Tensor) -> None:
+        n, h, w, _ = pred.shape
+        if split_pair(self.net, h, w):
+            f0, f1 = self.features(pred), self.features(tgt)
+        else:
+            f = self.features(torch.cat([pred, tgt]))
+            f0, f1 = [t[:n] for t in f], [t[n:] for t in f]
+        for k, (a, b) in enumerate(zip(f0, f1)):
+            layer_distance(a, b, self.lin[k], out=out, accumulate=k > 0)
+
+    def __call__(self, pred_u8: torch.Tensor, target_u8: torch.Tensor, chunk: Optional[int] = None) -> np.ndarray:
+        """chunk: pairs per backbone launch (default chunk_pairs(net, H, W)); it never changes a score."""
+        if pred_u8.shape != target_u8.shape or pred_u8.dim() != 4 or pred_u8.shape[3] != 3 \
+                or pred_u8.dtype != torch.uint8 or target_u8.dtype != torch.uint8:
+            raise ValueError("expected matching uint8 [N, H, W, 3] images")
+        n, h, w, _ = pred_u8.shape
+        step = min(chunk_pairs(self.net, h, w), int(chunk) if chunk else n) if n else 1  # validates the size
+        out = torch.empty(n, dtype=torch.float32, device=pred_u8.device)
+        for s0 in range(0, n, max(1, step)):
+            self._chunk(pred_u8[s0:s0 + step], target_u8[s0:s0 + step], out[s0:s0 + step])
+        return out.cpu().numpy().astype(np.float64)
+
+
+def max_pool(x: torch.Tensor, k: int, s: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Max pool of an fp32 NHWC activation: window k, stride s, no padding, floor mode."""
+    n, h, w, c = x.shape
+    if x.dtype != torch.float32 or h < k or w < k:
+        raise ValueError(f"max_pool: fp32 [n, h >= {k}, w >= {k}, c] expected, got {tuple(x.shape)} {x.dtype}")
+    ho, wo = (h - k) // s + 1, (w - k) // s + 1
+    if out is None:
+        out = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, ho, wo, c) or out.dtype != torch.float32:
+        raise ValueError(f"max_pool: out must be fp32 {(n, ho, wo, c)}")
+    ops.call("rdeic_maxpool2d", x.data_ptr(), n, h, w, c, ops.pix_ld(x), k, s, out.data_ptr(), ops.pix_ld(out),
+             ops.stream_ptr())
+    return out
+
+
+def layer_distance(f0: torch.Tensor, f1: torch.Tensor, lin: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   accumulate: bool = False) -> torch.Tensor:
+    """out[n] (+)= mean_p sum_c lin_c (f0 / (|f0_p| + 1e-10) - f1 / (|f1_p| + 1e-10))^2 of fp32 NHWC taps."""
+    if f0.shape != f1.shape or f0.dtype != torch.float32 or f1.dtype != torch.float32:
+        raise ValueError("layer_distance: two fp32 [n, h, w, c] taps of one shape expected")
+    n, h, w, c = f0.shape
+    if lin.dtype != torch.float32 or lin.numel() != c or not lin.is_contiguous():
+        raise ValueError(f"layer_distance: lin must be {c} contiguous fp32 weights")
+    if out is None:
+        if accumulate:
+            raise ValueError("layer_distance: accumulate needs out")
+        out = torch.empty(n, dtype=torch.float32, device=f0.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n,) or not out.is_contiguous():
+        raise ValueError(f"layer_distance: out must be contiguous fp32 [{n}]")
+    nf = int(_lib.load().rdeic_lpips_layer_ws_floats(n, h * w, c))
+    ws = torch.empty(max(nf, 1), dtype=torch.float32, device=f0.device)
+    ops.call("rdeic_lpips_layer", f0.data_ptr(), ops.pix_ld(f0), f1.data_ptr(), ops.pix_ld(f1), lin.data_ptr(), n,
+             h * w, c, int(accumulate), ws.data_ptr(), nf, out.data_ptr(), ops.stream_ptr())
+    return out

@@ -5,7 +5,8 @@ PSNR, SSIM and MS-SSIM as the reference's evaluation scripts report them
 definition (Wang et al. 2004; Wang, Simoncelli, Bovik 2003) with pyiqa's defaults — YIQ luma,
 11x11 Gaussian sigma 1.5, 'valid' windows, relu'd contrast-structure term, 5 scales — and are
 checked against the CPU restatement in oracle/metrics_ref.py; parity with pyiqa itself is unpinned.
-LPIPS needs an AlexNet backbone that is not available offline (out of scope)."""
+LPIPS (pyiqa "lpips": AlexNet, v0.1, inputs in [0, 1]) runs on the device too (rdeic_amd/lpips.py) with a
+backbone state dict the caller supplies; no backbone weights ship with the project."""
 from __future__ import annotations
 
 from typing import Tuple
@@ -48,3 +49,8 @@ def ssim_ms_ssim(pred_u8: torch.Tensor, target_u8: torch.Tensor) -> Tuple[np.nda
     w = np.asarray(MS_SSIM_WEIGHTS)
     ms = np.prod(lv[:, :-1, 1] ** w[:-1], axis=1) * lv[:, -1, 0] ** w[-1]
     return lv[:, 0, 0], ms
+
+
+def lpips(pred_u8: torch.Tensor, target_u8: torch.Tensor, model) -> np.ndarray:
+    """Per-image LPIPS [N] (float64) of uint8 [N,H,W,3] device tensors; model: an rdeic_amd.lpips.LPIPS."""
+    return model(pred_u8, target_u8)
