@@ -8,6 +8,7 @@ One step = one batch of B synthetic 512x512 OOD-satellite-shaped images per GPU 
 with the reference's precision (fp32, finetune_ood.yaml `precision: 32`) by default.
 
   python bench_train.py [--gpus N] [--steps K] [--warmup W] [--batch 1] [--size 512] [--dtype fp32|bf16]
+  python bench_train.py --refine ...     the refine step (is_refine) instead, eager
 For N > 1 run it as is (it starts N ranks itself, rdeic_amd/launch.py) or under torch.distributed.run
 (WORLD_SIZE must equal --gpus); one process per GPU, RCCL. Prints ONE JSON line.
 """
@@ -48,7 +49,17 @@ def parse(argv=None):
                     help="attention of the step (A/B; autograd.set_attention_impl; default: the library's)")
     ap.add_argument("--eager", action="store_true",
                     help="eager steps (default on one GPU: the step captured once as a hipGraph and replayed)")
+    ap.add_argument("--refine", action="store_true",
+                    help="the refine step (is_refine, fixed_step 2: sampler and VAE decoder in the loop, MSE + LPIPS) "
+                         "with a seeded AlexNet backbone; eager (its capture is out of scope)")
     return ap.parse_args(argv)
+
+
+def seeded_lpips(dev):
+    """LPIPS(alex) with the seeded stand-in backbone (none ships) and the published lin heads."""
+    from rdeic_amd import lpips as L
+    return L.LPIPS("alex", backbone=L.seeded_backbone("alex"),
+                   lin=os.path.join(ROOT, "tests", "golden", "lpips_lin.npz"), device=dev)
 
 
 def main(argv=None):
@@ -57,7 +68,7 @@ def main(argv=None):
     maybe_launch(args.gpus, __file__, sys.argv[1:] if argv is None else list(argv))
     from rdeic_amd import ops, parallel
     from rdeic_amd import finetune
-    from rdeic_amd.finetune import CapturedStep, FineTuner, nchw_draws_to_nhwc
+    from rdeic_amd.finetune import CapturedStep, FineTuneConfig, FineTuner, nchw_draws_to_nhwc
     finetune.FT_SPLITK = args.ft_splitk
     from rdeic_amd import autograd
     if args.train_attn:
@@ -68,7 +79,7 @@ def main(argv=None):
     if args.splitk_train:
         ops.SPLITK_TRAIN = tuple(int(v) for v in args.splitk_train.split(","))
     from rdeic_amd.rdeic import RDEIC
-    from rdeic_amd.synthetic import synth_context, synth_image, train_draws
+    from rdeic_amd.synthetic import refine_draws, synth_context, synth_image, train_draws
 
     rank, world, local = parallel.init_from_env()
     dev = torch.device("cuda", local)
@@ -81,7 +92,12 @@ def main(argv=None):
             print(f"[bench_train] {msg}", file=sys.stderr, flush=True)
 
     model = RDEIC(compute_dtype=dtype, device=dev).init_synthetic()
-    ft = FineTuner(model)
+    if args.refine:
+        args.eager = True
+        ft = FineTuner(model, FineTuneConfig(used_timesteps=model.used_timesteps, is_refine=True, fixed_step=2),
+                       lpips=seeded_lpips(dev))
+    else:
+        ft = FineTuner(model)
     if world > 1:
         ft.enable_ddp(bucket_bytes=args.bucket_mb << 20)
     log(f"{ft.num_params() / 1e6:.2f}M trainable parameters, world {world}, batch {B}/GPU, {S}x{S}, {args.dtype}")
@@ -90,7 +106,8 @@ def main(argv=None):
     ctx = synth_context().to(dev)
     slice_ch = model.cfg["compression"]["slice_ch"]
     total = args.warmup + args.steps + 1
-    draws = [nchw_draws_to_nhwc(train_draws(B, S // 8, S // 8, slice_ch, 7919 * rank + s, model.used_timesteps), dev)
+    draws = [nchw_draws_to_nhwc(refine_draws(B, S // 8, S // 8, slice_ch, 7919 * rank + s, 2) if args.refine else
+                                train_draws(B, S // 8, S // 8, slice_ch, 7919 * rank + s, model.used_timesteps), dev)
              for s in range(total)]
 
     def batch(s):
@@ -156,7 +173,9 @@ def main(argv=None):
                 "families": fam}
     if rank == 0:
         line = {
-            "metric": "adapter fine-tune (config 5) 512x512 images/s, UNet frozen, grad all-reduce; 1/2/4/8 GPU",
+            "metric": ("refine-stage training (is_refine, fixed_step 2) 512x512 images/s, eager, UNet frozen, grad "
+                       "all-reduce; 1/2/4/8 GPU") if args.refine else
+                      "adapter fine-tune (config 5) 512x512 images/s, UNet frozen, grad all-reduce; 1/2/4/8 GPU",
             "value": round(world * B * args.steps / elapsed, 3),
             "unit": "images/s",
             "n_gpus": world,
@@ -168,7 +187,10 @@ def main(argv=None):
             "vs_baseline": None,
             "dtype": args.dtype,
             "data": "synthetic (seeded OOD-satellite-shaped images, random-init weights, seeded draws)",
-            "config": {"workload": "config 5: adapter fine-tune step (control model + compressor trained, SD-2.1 "
+            "config": {"workload": ("refine step (is_refine, fixed_step 2: 2 relay sampler steps + VAE decoder in the "
+                                    "loop, image MSE + 0.5 LPIPS(alex, seeded backbone); control model + compressor "
+                                    "trained), AdamW lr 2e-5") if args.refine else
+                                   "config 5: adapter fine-tune step (control model + compressor trained, SD-2.1 "
                                    "UNet and VAE frozen), AdamW lr 2e-5",
                        "global_batch": world * B, "image_size": S, "parallelism": f"dp{world}",
                        "trainable_params": ft.num_params(), "steps_per_s": round(args.steps / elapsed, 4),

@@ -307,6 +307,31 @@ size_t rdeic_lpips_layer_ws_floats(int32_t n, int64_t hw, int32_t c);
 int rdeic_lpips_layer(const float* f0, int32_t ld0, const float* f1, int32_t ld1, const float* lin, int32_t n,
                       int64_t hw, int32_t c, int32_t accumulate, float* ws, size_t ws_floats, float* out,
                       void* stream);
+/* The backward of the LPIPS training loss (rdeic_amd/lpips.py LPIPS.loss), prediction side only. No kernel uses
+ * an atomic: every output element is one fixed-order sum and repeats bit for bit.
+ * prep of float images in [-1, 1]: img NHWC fp32 (dtype 0) / bf16 (1) with pixel stride ld >= 3 ->
+ * fp32 [npix][4] (16-byte aligned), channels 0..2 (v - shift_c) / scale_c, channel 3 zero. */
+int rdeic_lpips_prep_float(const void* img, int32_t ld, int32_t dtype, int64_t npix, float* out, void* stream);
+/* df0 [n][hw][c] (pixel stride ldd; += when accumulate) = gscore[img] * d(score of rdeic_lpips_layer)/d f0: with
+ * r = |f0_p|, s = r + 1e-10, n0 = f0 / s, n1 likewise, g_c = 2 lin_c (n0_c - n1_c) gscore[img] / hw,
+ * df0_c = g_c / s - f0_c (sum_c g_c f0_c) / (r s^2); exactly 0 at an all-zero pixel of f0. gscore: n device floats. */
+int rdeic_lpips_layer_bwd(const float* f0, int32_t ld0, const float* f1, int32_t ld1, const float* lin,
+                          const float* gscore, int32_t n, int64_t hw, int32_t c, int32_t accumulate, float* df0,
+                          int32_t ldd, void* stream);
+/* input gradient of rdeic_maxpool2d in gather form: dx [n][h][w][c] element = sum of dy over the windows that
+ * cover it and whose first maximum (row-major scan, strict >) it is, in output row-major order; 0 where no
+ * window covers it. in: the pool's input. */
+int rdeic_maxpool2d_bwd(const float* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ld_in, const float* dy,
+                        int32_t ld_dy, int32_t k, int32_t s, float* dx, int32_t ld_dx, void* stream);
+/* input gradient of a conv with cin <= 4 input channels, any kernel / stride / pad, in gather form.
+ * dz [n][ho][wo][cout] fp32 (cout % 4 == 0, ld % 4 == 0, 16-byte aligned), ho = (h + 2 pad - kh) / stride + 1;
+ * z (or NULL): the conv's output after its ReLU, the gradient passes where z > 0;
+ * wt: the weight as [kh][kw][cin][cout] fp32. dx [n][h][w] pixels with stride ld_dx, fp32 (dx_dtype 0) or bf16 (1):
+ * cin channels, or with prep_bwd the backward of rdeic_lpips_prep_float fused in: min(cin, 3) channels, each
+ * divided by scale_c. */
+int rdeic_conv_dgrad_small(const float* dz, int32_t ld_dz, const float* z, int32_t ld_z, const float* wt, int32_t n,
+                           int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride,
+                           int32_t pad, int32_t prep_bwd, void* dx, int32_t ld_dx, int32_t dx_dtype, void* stream);
 
 /* ------------------------------------------------------------ host coders
  * Gaussian-conditional tables (compressai 1.2.4 GaussianConditional.update, precision 16).

@@ -128,6 +128,11 @@ PROTOTYPES = {
     "rdeic_maxpool2d": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p]),
     "rdeic_lpips_layer_ws_floats": (_sz, [_i32, _i64, _i32]),
     "rdeic_lpips_layer": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i64, _i32, _i32, _p, _sz, _p, _p]),
+    "rdeic_lpips_prep_float": (C.c_int, [_p, _i32, _i32, _i64, _p, _p]),
+    "rdeic_lpips_layer_bwd": (C.c_int, [_p, _i32, _p, _i32, _p, _p, _i32, _i64, _i32, _i32, _p, _i32, _p]),
+    "rdeic_maxpool2d_bwd": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p, _i32, _p]),
+    "rdeic_conv_dgrad_small": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                         _i32, _i32, _p, _i32, _i32, _p]),
     "rdeic_groupnorm_parts_floats": (C.c_size_t, [_i64, _i32, _i32]),
     "rdeic_groupnorm_parts_ab": (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _i32, _f, _p, _p, _p, _p]),
     "rdeic_groupnorm_parts_apply": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _f, _p, _p,

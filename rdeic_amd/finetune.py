@@ -13,6 +13,11 @@ configs/model/rdeic_finetune_ood.yaml): sd_locked, is_refine False, so one step 
 and, with several ranks, the DDP gradient all-reduce of those ~76.7M parameters (bucketed, started
 from the backward as buckets complete: parallel.GradBuckets).
 
+With FineTuneConfig(is_refine=True) (the reference's configs/model/rdeic.yaml) the step is p_losses' other branch
+(rdeic.py:837-879): t = used_timesteps - 1, x_T = q_sample(c_latent), SpacedSampler.sample_grad with fixed_step
+steps, decode_first_stage_with_grad, loss = w (mse(image) + 0.5 LPIPS(image) + mse(c_latent, x_start)) + bpp + emb
+(refine_losses; LPIPS.loss of rdeic_amd/lpips.py). It runs eagerly: CapturedStep refuses it.
+
 Every op (forward and backward) runs through librdeic_hip.so (rdeic_amd/autograd.py); torch's
 autograd engine sequences them, and torch supplies device memory and the latent-sized elementwise
 loss glue. The trainable parameters live in ONE flat fp32 buffer (grads in another) so the
@@ -37,7 +42,9 @@ class FineTuneConfig:
     """configs/model/rdeic_finetune_ood.yaml + configs/finetune_ood.yaml (the values the step uses)."""
 
     def __init__(self, learning_rate=2e-5, l_guide_weight=3.0, l_bpp_weight=1.0, used_timesteps=300,
-                 betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, vq_beta=0.25, vq_decay=0.99, vq_temp=0.07):
+                 betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, vq_beta=0.25, vq_decay=0.99, vq_temp=0.07,
+                 is_refine=False, fixed_step=2):
+        self.is_refine, self.fixed_step = bool(is_refine), int(fixed_step)  # configs/model/rdeic.yaml: True, 2
         self.learning_rate = learning_rate
         self.l_guide_weight = l_guide_weight
         self.l_bpp_weight = l_bpp_weight
@@ -63,14 +70,19 @@ class FineTuner:
     """Holds the flat trainable parameters / grads / AdamW state of an RDEIC model and runs steps."""
 
     def __init__(self, model: RDEIC, cfg: Optional[FineTuneConfig] = None,
-                 embed_prob: Optional[torch.Tensor] = None):
-        """embed_prob: the VectorQuantiser's codebook-usage EMA buffer
+                 embed_prob: Optional[torch.Tensor] = None, lpips=None):
+        """lpips: an rdeic_amd.lpips.LPIPS (the reference's LPIPS(pnet_type='alex'), model/rdeic.py:653), needed by
+        the refine step (cfg.is_refine) only.
+        embed_prob: the VectorQuantiser's codebook-usage EMA buffer
         (`preprocess_model.quantize.embed_prob` of a reference checkpoint or of train.py's own; zeros
         when absent, as a freshly built VectorQuantiser, compression_modules.py:239-241). It sets which
         codes the next step re-initialises (decay = exp(-(embed_prob * N * 10) / (1 - 0.99) - 1e-3),
         compression_modules.py:272-296), so a resumed run must carry it."""
         self.m = model
         self.cfg = cfg or FineTuneConfig(used_timesteps=model.used_timesteps)
+        self.lpips = lpips
+        if self.cfg.is_refine and lpips is None:
+            raise ValueError("the refine step (is_refine) needs an LPIPS model: FineTuner(..., lpips=LPIPS('alex', ...))")
         st = model.store
         self.dtype = st.compute_dtype
         dev = st.device
@@ -368,6 +380,115 @@ class FineTuner:
                           guide_hint=guide_hint.detach())
         return loss, d
 
+    # ------------------------------------------------------------------ the refine step (is_refine: True)
+    def _vae_resnet(self, blk, x):
+        """ResnetBlock (ldm/modules/diffusionmodules/model.py:92-151), temb None."""
+        pre, cin, cout = blk
+        h, xs = self.gn(x, pre + ".norm1", 32, 1e-6, True, passthrough=True)
+        h = self.conv(h, pre + ".conv1")
+        h = self.gn(h, pre + ".norm2", 32, 1e-6, True)
+        skip = xs if cin == cout else self.conv(xs, pre + ".nin_shortcut")
+        return self.conv(h, pre + ".conv2", res=skip)
+
+    def _vae_attn(self, blk, x):
+        """AttnBlock (model.py:154-205): one head of width c; the materialised attention backward."""
+        pre, c = blk
+        B, H, W_, C = x.shape
+        h, xs = self.gn(x, pre + ".norm", 32, 1e-6, False, passthrough=True)
+        q = self.conv(h, pre + ".q").reshape(B * H * W_, C)
+        k = self.conv(h, pre + ".k").reshape(B * H * W_, C)
+        v = self.conv(h, pre + ".v").reshape(B * H * W_, C)
+        o = AG.attention(q, k, v, B, 1, int(C) ** (-0.5))
+        return self.conv(o.view(B, H, W_, C), pre + ".proj_out", res=xs)
+
+    def decode_first_stage_with_grad(self, z):
+        """decode_first_stage_with_grad (ddpm.py:847-855): 1 / scale_factor, post_quant_conv, Decoder.forward
+        (model.py:653-686) on the autograd Functions. z fp32 NHWC [B,h,w,4]; returns fp32 NHWC [B,8h,8w,3].
+        The decoder is frozen: its packed weights are cached under their parameter names."""
+        vae = self.m.first_stage_model
+        d = vae.prefix + "decoder."
+        h = AG.cast((1.0 / self.m.scale_factor) * z, self.dtype)
+        h = self.conv(h, vae.prefix + "post_quant_conv")
+        h = self.conv(h, d + "conv_in")
+        h = self._vae_resnet(vae.dec_mid[0], h)
+        h = self._vae_attn(vae.dec_mid[1], h)
+        h = self._vae_resnet(vae.dec_mid[2], h)
+        for lvl, up in vae.dec_blocks:
+            for blk in lvl:
+                h = self._vae_resnet(blk, h)
+            if up is not None:
+                h = self.conv(h, up, up2=True)
+        h = self.gn(h, d + "norm_out", 32, 1e-6, True)
+        return self.conv(h, d + "conv_out", out_f32=True)
+
+    def _refine_sampler(self):
+        """The relay spaced sampler with its float64 schedule for cfg.fixed_step steps, built once."""
+        cached = getattr(self, "_sampler", None)
+        if cached is None or cached[0] != self.cfg.fixed_step:
+            from .spaced_sampler_relay import SpacedSampler
+            sp = SpacedSampler(self.m)
+            sp.make_schedule(self.cfg.fixed_step)
+            cached = self._sampler = (self.cfg.fixed_step, sp)
+        return cached[1]
+
+    def sample_grad(self, x_T, guide_hint, ctx, step_noise):
+        """SpacedSampler.sample_grad (spaced_sampler_relay.py:193-268, 386-420) with cfg.fixed_step steps and
+        guidance scale 1: per step eps = noise_estimator(x), pred_x0 = A x - B eps, mean = C1 pred_x0 + C2 x,
+        x' = mean + S noise with the sampler's float64 schedule rounded to fp32 as the reference extracts it
+        (SpacedSampler.step_scalars); S = 0 at the last step, whose noise is still drawn. Differentiable fp32
+        ops on the latent; step_noise[i] fp32 NHWC, the i-th step's draw."""
+        sp = self._refine_sampler()
+        total = len(sp.timesteps)
+        if len(step_noise) < total:
+            raise ValueError(f"{total} steps need {total} noise tensors, got {len(step_noise)}")
+        x, B = x_T, x_T.shape[0]
+        for i, step in enumerate(sp.step_timesteps(self.cfg.fixed_step)):
+            a, b, c1, c2, s = sp.step_scalars(total - i - 1)
+            ts = torch.full((B,), int(step), dtype=torch.int64, device=x.device)
+            e = self.noise_estimator(x, guide_hint, ts, ctx)
+            pred_x0 = a * x - b * e
+            mean = c1 * pred_x0 + c2 * x
+            x = mean + s * step_noise[i]
+        return x
+
+    def refine_losses(self, x_start, h, ctx, target, noise, slice_noise, step_noise):
+        """p_losses' refine branch (rdeic.py:837-879) as written: t = used_timesteps - 1,
+        x_T = q_sample(c_latent, t, noise), samples = sample_grad, image = decode_first_stage_with_grad;
+        l_simple is logged and overwritten; loss = w l_mse + 0.5 w l_lpips + w l_guide (= T/loss) + l_bpp (bpp +
+        emb). target: the input image in [-1, 1], fp32 NHWC."""
+        m, cfg = self.m, self.cfg
+        c_latent, S, qS, emb_loss, guide_hint = self.compression_forward(h, slice_noise)
+        B, hl, wl, _ = x_start.shape
+        num_pixels = B * hl * wl * 64
+        bpp = AG.bpp_from_sum(S, num_pixels)
+        q_bpp = AG.bpp_from_sum(qS, num_pixels)
+        t = m.used_timesteps - 1
+        x_T = m.sqrt_alphas_cumprod[t] * c_latent + m.sqrt_one_minus_alphas_cumprod[t] * noise
+        samples = self.sample_grad(x_T, guide_hint, ctx, step_noise)
+        image = self.decode_first_stage_with_grad(samples)
+        loss_simple = ((samples - x_start) ** 2).mean(dim=(1, 2, 3))
+        loss_mse = ((image - target) ** 2).mean(dim=(1, 2, 3))
+        loss = cfg.l_guide_weight * loss_mse.mean()
+        loss_lpips = self.lpips.loss(image, target)
+        loss = loss + cfg.l_guide_weight * loss_lpips * 0.5
+        loss_guide = ((c_latent - x_start) ** 2).mean()
+        loss = loss + cfg.l_guide_weight * loss_guide
+        d = {"T/l_simple": loss_simple.mean(), "T/l_mse": loss_mse.mean(), "T/l_lpips": loss_lpips,
+             "T/l_guide": loss_guide, "T/loss": loss, "T/l_bpp": bpp[0], "T/q_bpp": q_bpp[0], "T/l_emb": emb_loss[0]}
+        loss = loss + cfg.l_bpp_weight * bpp[0]
+        loss = loss + cfg.l_bpp_weight * emb_loss[0]
+        self._last = dict(c_latent=c_latent.detach(), x_T=x_T.detach(), samples=samples, image=image,
+                          guide_hint=guide_hint.detach())
+        return loss, d
+
+    def image_target(self, img_u8: torch.Tensor) -> torch.Tensor:
+        """The batch's image in [-1, 1] as fp32 NHWC [B,H,W,3] (cond['target'], rdeic.py:679-686)."""
+        B, H, W_, _ = img_u8.shape
+        x = torch.empty((B, H, W_, 3), dtype=torch.float32, device=img_u8.device)
+        ops.call("rdeic_image_u8_to_nhwc", img_u8.contiguous().data_ptr(), B, H, W_, x.data_ptr(), 3, 0,
+                 ops.stream_ptr())
+        return x
+
     def zero_grad(self):
         self.grad.zero_()
         for n in self.offsets:  # direct-gradient use counts (autograd.count_direct_use) start at zero
@@ -407,8 +528,14 @@ class FineTuner:
         # training needs no batch invariance anywhere: small-M / large-K convs (B=1 UNet levels, input
         # gradients) may split K (deterministic, fixed-order reduction)
         with _ft_splitk_ctx(), AG.STEP_PACKS.active():
-            loss, d = self.losses(x_start, h, ctx, draws["t"], draws["noise"], draws["slice_noise"])
+            if self.cfg.is_refine:
+                loss, d = self.refine_losses(x_start, h, ctx, self.image_target(img_u8), draws["noise"],
+                                             draws["slice_noise"], draws["step_noise"])
+            else:
+                loss, d = self.losses(x_start, h, ctx, draws["t"], draws["noise"], draws["slice_noise"])
             loss.backward()
+        if self.cfg.is_refine:  # kept for inspection, without the graph
+            self._last = {k: v.detach() for k, v in self._last.items()}
         if self.buckets is not None:
             self.buckets.finish()
         elif sync_grads is not None:
@@ -444,6 +571,9 @@ class CapturedStep:
     def __init__(self, ft: "FineTuner", img_u8: torch.Tensor, ctx: torch.Tensor, draws: dict):
         if ft.buckets is not None:
             raise ValueError("graph capture is single-GPU (the DDP all-reduce runs from backward hooks)")
+        if ft.cfg.is_refine:
+            raise ValueError("graph capture of the refine step (is_refine) is out of scope: run it eagerly "
+                             "(FineTuner.training_step)")
         self.ft = ft
         self.img = img_u8.clone()
         self.ctx = ctx.clone()
@@ -497,5 +627,9 @@ class CapturedStep:
 def nchw_draws_to_nhwc(dr: dict, device) -> dict:
     """train_draws (NCHW, CPU) -> device NHWC fp32 tensors for FineTuner.training_step."""
     f = lambda a: a.permute(0, 2, 3, 1).contiguous().to(device=device, dtype=torch.float32)  # noqa: E731
-    return dict(t=dr["t"].to(device), post_eps=f(dr["post_eps"]), noise=f(dr["noise"]),
-                slice_noise=[f(s) for s in dr["slice_noise"]])
+    out = dict(post_eps=f(dr["post_eps"]), noise=f(dr["noise"]), slice_noise=[f(s) for s in dr["slice_noise"]])
+    if "t" in dr:
+        out["t"] = dr["t"].to(device)
+    if "step_noise" in dr:  # synthetic.refine_draws
+        out["step_noise"] = [f(s) for s in dr["step_noise"]]
+    return out

@@ -165,8 +165,20 @@ def load_lin(net: str, src: Union[str, Dict[str, torch.Tensor]]) -> List[torch.T
     return out
 
 
+def seeded_backbone(net: str, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A stand-in backbone for benchmarks (none ships): He-scaled normal weights and small normal biases from a
+    seeded generator, keyed as the torchvision state dict (features.<i>.*)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for i, _, cin, cout, k, _, _ in conv_layers(net):
+        sd[f"features.{i}.weight"] = torch.randn((cout, cin, k, k), generator=g) * (2.0 / (cin * k * k)) ** 0.5
+        sd[f"features.{i}.bias"] = torch.randn((cout,), generator=g) * 0.05
+    return sd
+
+
 class LPIPS:
-    """LPIPS(net)(pred_u8, target_u8): uint8 [N, H, W, 3] device tensors -> float64 numpy [N]."""
+    """LPIPS(net)(pred_u8, target_u8): uint8 [N, H, W, 3] device tensors -> float64 numpy [N].
+    LPIPS(net).loss(pred, target): the training loss of float images in [-1, 1], differentiable in pred."""
 
     def __init__(self, net: str = "alex", backbone=None, lin=None, device="cuda"):
         if backbone is None or lin is None:
@@ -176,7 +188,9 @@ class LPIPS:
         self.device = torch.device(device)
         self.table = _table(net)
         self.convs = []
-        for i, (wt, b) in enumerate(load_backbone(net, backbone)):
+        self._raw = load_backbone(net, backbone)  # CPU masters; the backward's device copies are made on first use
+        self._bwd = None
+        for i, (wt, b) in enumerate(self._raw):
             if i == 0:  # zero fourth input channel (the prep kernel's): exact zero products, 16-byte gathers
                 wt = torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, 1))
             _, _, _, _, _, s, p = conv_layers(net)[i]
@@ -225,6 +239,185 @@ class LPIPS:
         for s0 in range(0, n, max(1, step)):
             self._chunk(pred_u8[s0:s0 + step], target_u8[s0:s0 + step], out[s0:s0 + step])
         return out.cpu().numpy().astype(np.float64)
+
+    # ------------------------------------------------------------------ training loss
+    def _bwd_weights(self):
+        """(conv1's weight as [kh][kw][4][cout] for the gather dgrad, the other convs packed for the input-gradient
+        conv, autograd.conv_dgrad's form: flipped, [cin][kh kw cout] as a stride-1 conv with pad k - 1 - p).
+        Packed on first use and owned by this instance: they go when it goes."""
+        if self._bwd is None:
+            w0 = torch.nn.functional.pad(self._raw[0][0], (0, 0, 0, 0, 0, 1))
+            packs = [None]
+            for (w, _), (_, _, cin, cout, k, _, p) in zip(self._raw[1:], conv_layers(self.net)[1:]):
+                wd = w.to(self.device).contiguous()
+                wld = -(-(k * k * cout) // 64) * 64
+                packed = torch.empty((cin, wld), dtype=torch.float32, device=self.device)
+                ops.call("rdeic_pack_conv_weight_dgrad", wd.data_ptr(), cout, cin, k, k, packed.data_ptr(), wld, 0,
+                         ops.stream_ptr())
+                packs.append(ops.ConvParams(packed, wld, None, cin, cout, k, k, 1, k - 1 - p))
+            self._bwd = (w0.permute(2, 3, 1, 0).contiguous().to(self.device), packs)
+        return self._bwd
+
+    def forward_acts(self, x: torch.Tensor):
+        """Every activation of the prep output x [n, h, w, 4], x first, and the index of each tap in that list."""
+        acts, taps, ci = [x], [], 0
+        with ops.splitk_as((False, False)):
+            for op in self.table:
+                if op[0] == "conv":
+                    acts.append(ops.conv2d(acts[-1], self.convs[ci], act=ops.LEAKY, slope=0.0))
+                    ci += 1
+                elif op[0] == "pool":
+                    acts.append(max_pool(acts[-1], op[1], op[2]))
+                else:
+                    taps.append(len(acts) - 1)
+        return acts, taps
+
+    def features_float(self, img: torch.Tensor) -> List[torch.Tensor]:
+        """The five taps of float [n, H, W, 3] images in [-1, 1]."""
+        acts, taps = self.forward_acts(prep_float(img))
+        return [acts[i] for i in taps]
+
+    def loss(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """mean_n sum_k score_k (reference model/lpips.py:85-89 with inp_range (-1, 1)) of float NHWC device images
+        [N, H, W, 3] in [-1, 1], fp32 or bf16, as an fp32 device scalar. The gradient goes to pred only; the
+        backbone runs in fp32 whatever the image dtype."""
+        for t in (pred, target):
+            if t.dim() != 4 or t.shape[3] != 3 or t.dtype not in (torch.float32, torch.bfloat16) or not t.is_cuda:
+                raise ValueError("LPIPS.loss: float32 / bfloat16 [N, H, W, 3] device images expected")
+        if pred.shape != target.shape or pred.shape[0] == 0:
+            raise ValueError("LPIPS.loss: prediction and target must share a non-empty shape")
+        n, h, w, _ = pred.shape
+        if n * image_bytes(self.net, h, w) >= MAX_TENSOR_BYTES:  # validates the size; one backbone launch per side
+            raise ValueError(f"LPIPS.loss({self.net}) at {h}x{w}: {n} images' activations reach 2^31 bytes")
+        return _LossFn.apply(pred, target.detach(), self)
+
+
+class _LossFn(torch.autograd.Function):
+    """LPIPS.loss: forward and backward on the kernels of lpips.hip and the fp32 convs; torch only sequences."""
+
+    @staticmethod
+    def forward(ctx, pred, target, model: "LPIPS"):
+        n = pred.shape[0]
+        f1 = model.features_float(target)  # the target's other activations are dropped at once
+        acts, taps = model.forward_acts(prep_float(pred))
+        out = torch.empty(n, dtype=torch.float32, device=pred.device)
+        for k, i in enumerate(taps):
+            layer_distance(acts[i], f1[k], model.lin[k], out=out, accumulate=k > 0)
+        ctx.save_for_backward(*acts, *f1)  # kept until the graph is freed: a retained graph can run backward again
+        ctx.model, ctx.n_acts = model, len(acts)
+        ctx.pred_meta = (tuple(pred.shape), pred.dtype)
+        ctx.splitk = ops.splitk_state()  # the backward runs on autograd's thread: the dgrads split K as allowed here
+        return out.mean()
+
+    @staticmethod
+    def backward(ctx, gout):
+        model, saved = ctx.model, ctx.saved_tensors
+        acts, f1 = saved[:ctx.n_acts], saved[ctx.n_acts:]
+        (n, h, w, _), dtype = ctx.pred_meta
+        gscore = (gout.to(torch.float32) / n).expand(n).contiguous()
+        w0, packs = model._bwd_weights()
+        # forward records: (op, activation index of its input)
+        recs, i, ci, k = [], 0, 0, 0
+        for op in model.table:
+            if op[0] == "tap":
+                recs.append(("tap", i, k))
+                k += 1
+            else:
+                recs.append((op, i, ci))
+                i += 1
+                ci += op[0] == "conv"
+        d = dpred = None
+        with ops.splitk_as(ctx.splitk):
+            for op, i, j in reversed(recs):
+                if op == "tap":
+                    d = layer_distance_bwd(acts[i], f1[j], model.lin[j], gscore, out=d)
+                elif d is None:
+                    continue  # nothing after the last tap
+                elif op[0] == "pool":
+                    d = max_pool_bwd(acts[i], d, op[1], op[2])
+                elif j == 0:
+                    _, _, cout, ks, s, p = op
+                    dpred = torch.empty((n, h, w, 3), dtype=dtype, device=d.device)
+                    conv_dgrad_small(d, acts[1], w0, (h, w), 4, ks, s, p, prep_bwd=True, out=dpred)
+                else:
+                    _, _, cout, ks, s, p = op
+                    z = acts[i + 1]
+                    ops.call("rdeic_act_bwd", d.data_ptr(), ops.pix_ld(d), z.data_ptr(), ops.pix_ld(z),
+                             d.numel() // cout, cout, ops.LEAKY, 0.0, d.data_ptr(), ops.pix_ld(d), 0,
+                             ops.stream_ptr())  # the ReLU mask, in place
+                    d = ops.conv2d(d, packs[j], out_hw=tuple(acts[i].shape[1:3]))  # stride 1 throughout
+        return dpred, None, None
+
+
+def prep_float(img: torch.Tensor) -> torch.Tensor:
+    """The ScalingLayer for inputs in [-1, 1]: float NHWC [n, h, w, 3] (fp32 / bf16, any pixel stride) ->
+    fp32 [n, h, w, 4], channels 0..2 (v - shift_c) / scale_c, channel 3 zero."""
+    n, h, w, _ = img.shape
+    x = torch.empty((n, h, w, 4), dtype=torch.float32, device=img.device)
+    try:
+        ld = ops.pix_ld(img)
+    except ValueError:
+        img = img.contiguous()
+        ld = 3
+    ops.call("rdeic_lpips_prep_float", img.data_ptr(), ld, ops.dt_code(img), n * h * w, x.data_ptr(),
+             ops.stream_ptr())
+    return x
+
+
+def layer_distance_bwd(f0: torch.Tensor, f1: torch.Tensor, lin: torch.Tensor, gscore: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gscore[n] * d layer_distance(f0, f1, lin)[n] / d f0, written to a new tensor or added to out. An all-zero
+    pixel of f0 gets exactly 0."""
+    if f0.shape != f1.shape or f0.dtype != torch.float32 or f1.dtype != torch.float32:
+        raise ValueError("layer_distance_bwd: two fp32 [n, h, w, c] taps of one shape expected")
+    n, h, w, c = f0.shape
+    if lin.dtype != torch.float32 or lin.numel() != c or not lin.is_contiguous():
+        raise ValueError(f"layer_distance_bwd: lin must be {c} contiguous fp32 weights")
+    if gscore.dtype != torch.float32 or tuple(gscore.shape) != (n,) or not gscore.is_contiguous():
+        raise ValueError(f"layer_distance_bwd: gscore must be contiguous fp32 [{n}]")
+    acc = out is not None
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=f0.device)
+    elif out.shape != f0.shape or out.dtype != torch.float32:
+        raise ValueError(f"layer_distance_bwd: out must be fp32 {tuple(f0.shape)}")
+    ops.call("rdeic_lpips_layer_bwd", f0.data_ptr(), ops.pix_ld(f0), f1.data_ptr(), ops.pix_ld(f1), lin.data_ptr(),
+             gscore.data_ptr(), n, h * w, c, int(acc), out.data_ptr(), ops.pix_ld(out), ops.stream_ptr())
+    return out
+
+
+def max_pool_bwd(x: torch.Tensor, dy: torch.Tensor, k: int, s: int) -> torch.Tensor:
+    """Input gradient of max_pool(x, k, s): torch's rule (the first maximum of a window takes its gradient)."""
+    n, h, w, c = x.shape
+    ho, wo = (h - k) // s + 1, (w - k) // s + 1
+    if x.dtype != torch.float32 or dy.dtype != torch.float32 or tuple(dy.shape) != (n, ho, wo, c):
+        raise ValueError(f"max_pool_bwd: fp32 x and dy {(n, ho, wo, c)} expected, got {tuple(dy.shape)}")
+    dx = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    ops.call("rdeic_maxpool2d_bwd", x.data_ptr(), n, h, w, c, ops.pix_ld(x), dy.data_ptr(), ops.pix_ld(dy), k, s,
+             dx.data_ptr(), c, ops.stream_ptr())
+    return dx
+
+
+def conv_dgrad_small(dz: torch.Tensor, z: Optional[torch.Tensor], wt: torch.Tensor, in_hw, cin: int, k: int,
+                     stride: int, pad: int, prep_bwd: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Input gradient of a conv with cin <= 4 (any kernel, stride, pad) from dz [n, ho, wo, cout] fp32.
+    z: the conv's output after its ReLU (mask z > 0), or None. wt: the weight as [k][k][cin][cout] fp32.
+    prep_bwd: also the backward of prep_float (3 channels, each / scale_c). out: [n, h, w, channels] fp32 / bf16."""
+    n, ho, wo, cout = dz.shape
+    h, w = in_hw
+    if dz.dtype != torch.float32 or tuple(wt.shape) != (k, k, cin, cout) or wt.dtype != torch.float32 \
+            or not wt.is_contiguous() or (ho, wo) != ((h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1):
+        raise ValueError("conv_dgrad_small: dz fp32 [n, ho, wo, cout] and wt fp32 [k, k, cin, cout] expected")
+    if z is not None and (z.shape != dz.shape or z.dtype != torch.float32):
+        raise ValueError("conv_dgrad_small: z must match dz")
+    co = min(cin, 3) if prep_bwd else cin
+    if out is None:
+        out = torch.empty((n, h, w, co), dtype=torch.float32, device=dz.device)
+    elif tuple(out.shape) != (n, h, w, co):
+        raise ValueError(f"conv_dgrad_small: out must be {(n, h, w, co)}")
+    ops.call("rdeic_conv_dgrad_small", dz.data_ptr(), ops.pix_ld(dz), None if z is None else z.data_ptr(),
+             0 if z is None else ops.pix_ld(z), wt.data_ptr(), n, h, w, cin, cout, k, k, stride, pad, int(prep_bwd),
+             out.data_ptr(), ops.pix_ld(out), ops.dt_code(out), ops.stream_ptr())
+    return out
 
 
 def max_pool(x: torch.Tensor, k: int, s: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -54,3 +54,17 @@ def train_draws(batch: int, h: int, w: int, slice_ch, seed: int, used_timesteps:
     slice_noise = [torch.rand((batch, c, hy, wy), generator=g) - 0.5 for c in slice_ch]
     noise = torch.randn((batch, 4, h, w), generator=g)
     return dict(t=t, post_eps=post_eps, slice_noise=slice_noise, noise=noise)
+
+
+def refine_draws(batch: int, h: int, w: int, slice_ch, seed: int, fixed_step: int = 2):
+    """The random draws of one refine step (is_refine: True; model/rdeic.py:774-776, 837-848), from one CPU
+    generator in the reference's order: the posterior sample's randn (distributions.py:36), one U(-0.5, 0.5) per
+    entropy slice in slice order, the q_sample randn of x_T (rdeic.py:840), then one randn per sampler step
+    (spaced_sampler_relay.py:414), the masked last step's included. No t is drawn: t = used_timesteps - 1."""
+    g = torch.Generator().manual_seed(int(seed))
+    post_eps = torch.randn((batch, 4, h, w), generator=g)
+    hy, wy = h // 2, w // 2
+    slice_noise = [torch.rand((batch, c, hy, wy), generator=g) - 0.5 for c in slice_ch]
+    noise = torch.randn((batch, 4, h, w), generator=g)
+    step_noise = [torch.randn((batch, 4, h, w), generator=g) for _ in range(fixed_step)]
+    return dict(post_eps=post_eps, slice_noise=slice_noise, noise=noise, step_noise=step_noise)

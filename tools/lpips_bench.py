@@ -3,6 +3,7 @@ backbone convs and the three lpips.hip kernels, with each kernel's achieved byte
 needs, from shapes, over the event-timed launch). Seeded random backbone, random heads, synthetic images.
 
     python tools/lpips_bench.py [--net alex] [--pairs 16] [--size 512] [--reps 20] [--out FILE.json]
+    python tools/lpips_bench.py --loss [--pairs 1] ...   the training loss LPIPS.loss, forward + backward
 """
 import argparse
 import json
@@ -21,16 +22,6 @@ if ROOT not in sys.path:
 HBM_ACHIEVABLE = 6.3e12  # bytes/s, float4 copy on this part
 
 
-def seeded_backbone(net, seed=0):
-    from rdeic_amd import lpips as L
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for i, _, cin, cout, k, _, _ in L.conv_layers(net):
-        sd[f"features.{i}.weight"] = torch.randn((cout, cin, k, k), generator=g) * (2.0 / (cin * k * k)) ** 0.5
-        sd[f"features.{i}.bias"] = torch.randn((cout,), generator=g) * 0.05
-    return sd
-
-
 def timed(fn, reps):
     """Median milliseconds of fn() by device events, after 3 warm-up calls."""
     for _ in range(3):
@@ -46,8 +37,82 @@ def timed(fn, reps):
     return statistics.median(ms)
 
 
+def bench_loss(a, m):
+    """LPIPS.loss forward + backward on float images: the whole call (host clock, synchronised), the peak of
+    device memory over it, and the backward's own kernels by device events."""
+    from rdeic_amd import lpips as L
+    from rdeic_amd.synthetic import synth_image
+    n, s = a.pairs, a.size
+    tgt = torch.from_numpy(np.stack([synth_image(s, s, 100 + i) for i in range(n)])).float() / 127.5 - 1.0
+    g = torch.Generator().manual_seed(0)
+    pred = (tgt + torch.randn(tgt.shape, generator=g) * (12.0 / 127.5)).clamp(-1, 1)
+    p, t = pred.cuda().requires_grad_(True), tgt.cuda()
+
+    def step():
+        p.grad = None
+        m.loss(p, t).backward()
+
+    def fwd():
+        with torch.no_grad():
+            m.loss(p, t)
+
+    def wall(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ms), min(ms)
+
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    step_ms, step_min = wall(step)
+    peak = torch.cuda.max_memory_allocated() - base
+    fwd_ms, _ = wall(fwd)
+    res = {"mode": "loss", "net": a.net, "pairs": n, "size": s, "fwd_bwd_ms": step_ms, "fwd_bwd_ms_min": step_min,
+           "fwd_ms": fwd_ms, "peak_bytes_over_inputs": peak, "ops": []}
+
+    def add(name, ms, nbytes):
+        res["ops"].append({"name": name, "ms": ms, "bytes": nbytes, "TBps": nbytes / (ms * 1e-3) / 1e12})
+
+    acts, taps = m.forward_acts(L.prep_float(p.detach()))
+    f1 = m.features_float(t)
+    gs = torch.full((n,), 1.0 / n, device="cuda")
+    add(f"prep_float {n}x{s}x{s}", timed(lambda: L.prep_float(t), a.reps), n * s * s * (12 + 16))
+    for k, i in enumerate(taps):
+        f0, lv, fb = acts[i], m.lin[k], f1[k]
+        add(f"layer_bwd{k} {tuple(f0.shape)}", timed(lambda: L.layer_distance_bwd(f0, fb, lv, gs), a.reps),
+            4 * 3 * f0.numel())
+    i = 0
+    for op in m.table:
+        if op[0] == "pool":
+            xin = acts[i]
+            dy = torch.randn_like(acts[i + 1])
+            add(f"pool_bwd{op[1]}/{op[2]} {tuple(xin.shape)}", timed(lambda: L.max_pool_bwd(xin, dy, op[1], op[2]), a.reps),
+                4 * (2 * xin.numel() + dy.numel()))
+        i += op[0] != "tap"
+    w0, _ = m._bwd_weights()
+    _, _, _, ks, st, pd = m.table[0]
+    dz, dx = torch.randn_like(acts[1]), torch.empty((n, s, s, 3), device="cuda")
+    add(f"conv1 dgrad (gather, k{ks}/{st}) {tuple(dz.shape)}",
+        timed(lambda: L.conv_dgrad_small(dz, acts[1], w0, (s, s), 4, ks, st, pd, prep_bwd=True, out=dx), a.reps),
+        4 * (2 * dz.numel() + dx.numel()))
+    for r in res["ops"]:
+        print(f"{r['name']:64s} {r['ms']:8.4f} ms  {r['TBps']:.3f} TB/s")
+    print(json.dumps({k_: v for k_, v in res.items() if k_ != "ops"}))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--loss", action="store_true", help="time LPIPS.loss forward + backward instead of the metric")
     ap.add_argument("--net", default="alex", choices=["alex", "vgg"])
     ap.add_argument("--pairs", type=int, default=16)
     ap.add_argument("--size", type=int, default=512)
@@ -60,7 +125,9 @@ def main():
     from rdeic_amd.synthetic import synth_image
     g = torch.Generator().manual_seed(1)
     lin = {f"lin{k}": torch.rand(c, generator=g) * 0.1 for k, c in enumerate(L.CHANNELS[a.net])}
-    m = L.LPIPS(a.net, backbone=seeded_backbone(a.net), lin=lin)
+    m = L.LPIPS(a.net, backbone=L.seeded_backbone(a.net), lin=lin)
+    if a.loss:
+        return bench_loss(a, m)
     n, s = a.pairs, a.size
     tgt = np.stack([synth_image(s, s, 100 + i) for i in range(n)])
     rng = np.random.default_rng(0)

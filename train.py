@@ -6,8 +6,11 @@
 One process per GPU (RCCL): every rank trains on its own synthetic batches; gradients of the
 control model + compressor are all-reduced in buckets from the backward (FineTuner.enable_ddp).
 Weights: random-init synthetic (rdeic_amd/weights.py) or `model.resume` (reference-named state
-dict, loaded with safe loaders only). Logs the reference's loss dict (T/loss, T/l_simple, T/l_bpp,
-T/q_bpp, T/l_emb, T/l_guide) every log_every_n_steps and saves the trainable parameters (and the
+dict, loaded with safe loaders only). With `is_refine: true` (configs/refine.yaml, the reference's
+configs/model/rdeic.yaml) the step is p_losses' refine branch: the relay sampler and the VAE decoder in the loop,
+image MSE + 0.5 LPIPS(alex); it needs model.lpips_backbone / model.lpips_lin and runs eagerly. Logs the reference's
+loss dict (T/loss, T/l_simple, T/l_bpp, T/q_bpp, T/l_emb, T/l_guide; refine: also T/l_mse, T/l_lpips) every
+log_every_n_steps and saves the trainable parameters (and the
 AdamW state) every every_n_train_steps as safetensors.
 """
 from __future__ import annotations
@@ -79,25 +82,36 @@ def main(argv=None):
         autograd.set_attention_impl(args.attention)
     from rdeic_amd.finetune import CapturedStep, FineTuneConfig, FineTuner, nchw_draws_to_nhwc
     from rdeic_amd.rdeic import RDEIC
-    from rdeic_amd.synthetic import synth_context, synth_image, train_draws
+    from rdeic_amd.synthetic import refine_draws, synth_context, synth_image, train_draws
 
-    rank, world, local = parallel.init_from_env()
-    dev = torch.device("cuda", local)
     mc, dc, lc = cfg["model"], cfg["data"], cfg["lightning"]
     dtype = precision_dtype(mc.get("precision", 32))
     seed = int(lc.get("seed", 231))
-    if not mc.get("sd_locked", True) or mc.get("is_refine", False):
-        raise SystemExit("only the light adaptation (sd_locked: true, is_refine: false) is supported")
+    if not mc.get("sd_locked", True):
+        raise SystemExit("sd_locked: false (training the UNet decoder) is not supported")
+    refine = bool(mc.get("is_refine", False))
+    if refine:  # p_losses' refine branch trains on LPIPS(alex); no backbone weights ship with the project
+        for key in ("lpips_backbone", "lpips_lin"):
+            if not mc.get(key) or not os.path.isfile(str(mc[key])):
+                raise SystemExit(f"is_refine: true needs model.{key}: the torchvision AlexNet state dict "
+                                 f"(lpips_backbone) and the LPIPS lin heads (lpips_lin); got {mc.get(key)!r}")
+    rank, world, local = parallel.init_from_env()
+    dev = torch.device("cuda", local)
     model = RDEIC(compute_dtype=dtype, device=dev).init_synthetic()
     sd, meta = (load_state(mc["resume"]) if mc.get("resume") else ({}, {}))
     if sd:
         model.load_state_dict(sd, strict=False)
+    lpips = None
+    if refine:
+        from rdeic_amd.lpips import LPIPS
+        lpips = LPIPS("alex", backbone=str(mc["lpips_backbone"]), lin=str(mc["lpips_lin"]), device=dev)
     # the codebook-usage EMA travels with the weights (reference checkpoints and ours)
     ft = FineTuner(model, FineTuneConfig(learning_rate=float(mc["learning_rate"]),
                                          l_guide_weight=float(mc["l_guide_weight"]),
                                          l_bpp_weight=float(mc["l_bpp_weight"]),
-                                         used_timesteps=int(mc["used_timesteps"])),
-                   embed_prob=sd.get(EMBED_PROB))
+                                         used_timesteps=int(mc["used_timesteps"]), is_refine=refine,
+                                         fixed_step=int(mc.get("fixed_step", 2))),
+                   embed_prob=sd.get(EMBED_PROB), lpips=lpips)
     start = 0
     if "optimizer.exp_avg" in sd:  # one of train.py's own checkpoints: continue that run exactly
         start = int(meta.get("global_step", 0))
@@ -123,10 +137,11 @@ def main(argv=None):
     t0 = time.perf_counter()
     for step in range(start + 1, max_steps + 1):
         idx = rng.integers(0, n_img, size=B)
-        dr = nchw_draws_to_nhwc(train_draws(B, S // 8, S // 8, slice_ch, seed * 1000003 + step * 131 + rank,
-                                            ft.cfg.used_timesteps), dev)
+        dseed = seed * 1000003 + step * 131 + rank
+        dr = nchw_draws_to_nhwc(refine_draws(B, S // 8, S // 8, slice_ch, dseed, ft.cfg.fixed_step) if refine else
+                                train_draws(B, S // 8, S // 8, slice_ch, dseed, ft.cfg.used_timesteps), dev)
         batch = pool[torch.from_numpy(idx).to(dev)]
-        if world == 1 and not args.eager and graph is None:
+        if world == 1 and not args.eager and not refine and graph is None:  # the refine step runs eagerly
             graph = CapturedStep(ft, batch, ctx, dr)  # one GPU: the step replays as one hipGraph
         d = graph.step(batch, dr) if graph is not None else ft.training_step(batch, ctx, dr)
         if rank == 0 and (step % log_every == 0 or step == max_steps):
