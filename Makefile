@@ -48,3 +48,6 @@ $(BUILD)/conv_gemm.hip.o $(BUILD)/conv_dma.hip.o $(BUILD)/conv_halo.hip.o $(BUIL
 
 # training flash attention: as attention.hip (the softmax / dS arithmetic reads every MFMA result)
 $(BUILD)/attention_bwd.hip.o: HIPFLAGS += -mllvm -amdgpu-mfma-vgpr-form=1
+
+# causal attention of the text tower: the same accumulator form, for the same reason
+$(BUILD)/attention_causal.hip.o: HIPFLAGS += -mllvm -amdgpu-mfma-vgpr-form=1

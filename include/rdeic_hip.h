@@ -201,6 +201,23 @@ int rdeic_attention(const void* q, int32_t ldq, const void* k, int32_t ldk, cons
 int rdeic_softmax_rows(const float* s, int64_t rows, int32_t cols, float scale, void* p, int32_t dtype, void* stream);
 int rdeic_transpose(const void* in, int32_t rows, int32_t cols, int32_t ldin, void* out, int32_t ldout,
                     int32_t batch, int64_t in_bs, int64_t out_bs, int32_t dtype, void* stream);
+/* Causal self-attention of the OpenCLIP text tower (ldm/modules/encoders/modules.py:216-233
+ * text_transformer_forward with open_clip's build_attention_mask: upper-triangular -inf, no padding mask):
+ * o_i = softmax_{j <= i}(q_i . k_j * scale) v_j per (batch, head), the 'b n (h d)' layout of rdeic_attention
+ * with lq = lk = l. dh must be 64 (ViT-H/14 text: 16 heads of 64); any l >= 1. dtype 1: bf16 with fp32
+ * accumulation; 0: fp32 on v_mfma_f32_16x16x4_f32. q / k / v 16-byte aligned with strides a multiple of 8
+ * (bf16) / 4 (fp32); o 8-byte (bf16) / 16-byte (fp32) aligned with a stride that is a multiple of 4. A row's
+ * result depends on its own (batch, head) only and repeats bit for bit. Counted under RDEIC_PROF_ATTN with the
+ * lower triangle's 4*B*H*dh*l(l+1)/2 FLOPs. */
+int rdeic_attention_causal(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv,
+                           void* o, int32_t ldo, int32_t batch, int32_t heads, int32_t l, int32_t dh,
+                           float scale, int32_t dtype, void* stream);
+/* x = token_embedding[tokens] + positional_embedding (modules.py:207-208 encode_with_transformer): out[b*context
+ * + t][0..width) = table[tokens[b][t]] + pos[t], fp32 tables, summed in fp32, written in `dtype`. tokens: device
+ * int32 [batch][context]; the caller has checked 0 <= id < vocab on the host. */
+int rdeic_embed_tokens(const float* table, int32_t ld_table, const float* pos, int32_t ld_pos, const int32_t* tokens,
+                       int32_t batch, int32_t context, int32_t width, void* out, int32_t ld_out, int32_t dtype,
+                       void* stream);
 
 /* ----------------------------------------------------------- elementwise */
 /* x * gelu(gate) where x = in[:, :c], gate = in[:, c:2c] (GEGLU, attention.py:49-56) */
@@ -392,7 +409,8 @@ int rdeic_ac_uniform_cdf(int32_t codebook_size, int16_t* cdf_row);
  * algorithmic work (FLOPs for conv / attention, bytes for GroupNorm) and the event-timed ms
  * (it synchronizes on the recorded events). rdeic_prof_stop returns the slots used. */
 #define RDEIC_PROF_CONV 0        /* rdeic_conv2d / _tile / _splitk (incl. batched GEMMs): 2*M*N*K FLOPs */
-#define RDEIC_PROF_ATTN 1        /* rdeic_attention, head dim >= 64: 4*B*H*Lq*Lk*dh FLOPs */
+#define RDEIC_PROF_ATTN 1        /* rdeic_attention, head dim >= 64: 4*B*H*Lq*Lk*dh FLOPs; rdeic_attention_causal:
+                                    the lower triangle, 4*B*H*dh*l(l+1)/2 */
 #define RDEIC_PROF_ATTN_SMALL 2  /* rdeic_attention, head dim < 64 */
 #define RDEIC_PROF_GN_STATS 3    /* rdeic_groupnorm_stats: bytes read */
 #define RDEIC_PROF_GN_APPLY 4    /* rdeic_groupnorm_apply: bytes read + written */

@@ -7,7 +7,9 @@ decompress -> q_sample at t=used_timesteps-1 -> relay DDIM -> VAE decode -> crop
 Differences from the reference, all forced by the offline image:
   * no checkpoint is shipped: without --ckpt the model uses the seeded synthetic weights;
     with --ckpt, a plain state dict is read with torch.load(weights_only=True);
-  * the OpenCLIP "" embedding (reference :122) is replaced by the seeded synthetic context;
+  * the OpenCLIP "" embedding (reference :122) comes from model.get_learned_conditioning([""]) when the
+    checkpoint holds the text tower (cond_stage_model.model.*); without one (synthetic weights, or a checkpoint
+    stripped of it) the seeded synthetic context stands in;
   * the noise draws (x_T, q_sample noise, and the spaced sampler's per-step randn_like) come from a
     seeded CPU generator in the reference's order, not from the device RNG.
 The noise draws follow the reference order (inference.py:64-65: a discarded randn, then noise).
@@ -110,7 +112,10 @@ def main(argv=None) -> None:
         raise SystemExit(f"--input {args.input} is not a directory")
     gen = torch.Generator().manual_seed(args.seed)
     model = load_model(args.ckpt, args.dtype)
-    c_crossattn = [synth_context().to(model.device)]
+    if model.cond_stage_model is not None:
+        c_crossattn = [model.get_learned_conditioning([""])]  # reference inference.py:122
+    else:
+        c_crossattn = [synth_context().to(model.device)]
     print(f"sampling {args.steps} steps using {args.sampler} sampler")
     bpps = []
     for file_path in list_image_files(args.input):

@@ -5,6 +5,7 @@
         [--steps 2] [--sampler ddpm|ddim] [--bf16 | --fp16] [--enable_resize_guard --max_long_side 1024
         --upsample_to_original] [--save_intermediates] [--max_images N]
         [--lpips_backbone PATH [--lpips_lin PATH] [--lpips_net alex|vgg]]
+        [--captions_file FILE.json --clip_vocab bpe_simple_vocab_16e6.txt.gz]
 
 What it keeps from the reference:
   * images are grouped by their padded (multiple-of-64) working size after the optional resize
@@ -20,8 +21,14 @@ What it keeps from the reference:
   * --save_intermediates writes the decoded latent (.pt / .npy), a guide-hint preview and a
     preview decode of c_latent per image (:188-233); --profile_memory prints device memory.
 What differs, all forced by the offline image or by design:
-  * captioning (--use_captions, Qwen2-VL) and OpenCLIP text encoding are out of scope: the seeded
-    synthetic context stands in for the "" embedding, and --use_captions is refused;
+  * the "" context comes from model.get_learned_conditioning([""]) (the OpenCLIP text tower on the device,
+    rdeic_amd/text.py) when the checkpoint holds the tower; without one the seeded synthetic context stands in;
+  * captioning (--use_captions, Qwen2-VL) is out of scope and refused. Captions made elsewhere are read with
+    --captions_file FILE.json ({image path relative to --input: caption}): each image is then conditioned on
+    its caption's embedding, the "" embedding is the unconditional branch of classifier-free guidance
+    (--guidance_scale), as the reference's :487-493, and metrics.csv gains a `caption` column. It needs a
+    loaded tower and CLIP's BPE vocabulary (--clip_vocab or RDEIC_CLIP_VOCAB; rdeic_amd/tokenizer.py), and is
+    refused at start-up without either;
   * --bf16 selects the bf16 compute path; the default is the fp32 parity path. The reference's
     --fp16 (autocast float16) is accepted and selects the same bf16 path with a notice on stderr:
     no float16 kernels are built for MI355X;
@@ -202,7 +209,21 @@ def parse_args(argv=None) -> Namespace:
     p.add_argument("--lpips_lin", type=str, default="",
                    help="the LPIPS lin heads (.pth as the reference's, or .npz); default ./weight/lpips/<net>.pth")
     p.add_argument("--lpips_net", type=str, default="alex", choices=["alex", "vgg"])
+    p.add_argument("--captions_file", type=str, default="",
+                   help="JSON {image path relative to --input: caption}: per-image text conditioning with "
+                        "classifier-free guidance against the \"\" embedding (needs the text tower and --clip_vocab)")
+    p.add_argument("--clip_vocab", type=str, default="",
+                   help="CLIP's BPE vocabulary bpe_simple_vocab_16e6.txt.gz (default: $RDEIC_CLIP_VOCAB)")
     args = p.parse_args(argv)
+    if args.captions_file:  # refused at start-up, before any model is built
+        if not os.path.isfile(args.captions_file):
+            p.error(f"--captions_file {args.captions_file} is not a file")
+        args.clip_vocab = args.clip_vocab or os.environ.get("RDEIC_CLIP_VOCAB", "")
+        if not args.clip_vocab:
+            p.error("--captions_file needs CLIP's BPE vocabulary bpe_simple_vocab_16e6.txt.gz: pass --clip_vocab "
+                    "or set RDEIC_CLIP_VOCAB")
+        if not os.path.isfile(args.clip_vocab):
+            p.error(f"--clip_vocab {args.clip_vocab} is not a file")
     if args.lpips_backbone:  # refused at start-up, not a NaN column at the end
         if not args.lpips_lin:
             args.lpips_lin = os.path.join(".", "weight", "lpips", f"{args.lpips_net}.pth")
@@ -247,7 +268,18 @@ def main(argv=None) -> List[Dict]:
         from rdeic_amd.lpips import LPIPS
         lpips_model = LPIPS(args.lpips_net, backbone=args.lpips_backbone, lin=args.lpips_lin)
     model = _load(args)
-    ctx = synth_context().to(model.device)
+    captions: Optional[Dict[str, str]] = None
+    if args.captions_file:
+        if model.cond_stage_model is None:
+            raise SystemExit("--captions_file needs the OpenCLIP text tower: the checkpoint holds no "
+                             "cond_stage_model.model.* weights")
+        import json
+        with open(args.captions_file) as fh:
+            captions = {os.path.normpath(k): str(v) for k, v in json.load(fh).items()}
+    if model.cond_stage_model is not None:
+        ctx = model.get_learned_conditioning([""])  # reference :493
+    else:
+        ctx = synth_context().to(model.device)
     os.makedirs(args.output, exist_ok=True)
     print(f"sampling {args.steps} steps using {args.sampler} sampler")
     files = sorted(list_image_files(args.input))
@@ -286,14 +318,20 @@ def main(argv=None) -> List[Dict]:
                 streams.append(os.path.join(parent, "data", stem))
                 prefixes.append(os.path.join(parent, stem))
                 targets.append((np.array(full), np.array(scaled), rel))
+            c_crossattn, uc_crossattn, texts = [ctx], None, None
+            if captions is not None:  # reference :487-491
+                texts = [captions.get(os.path.normpath(t[2]), "") for t in targets]
+                c_crossattn = [model.get_learned_conditioning(texts, vocab_path=args.clip_vocab)]
+                uc_crossattn = [ctx]
             t0 = time.time()
-            preds, bpp_batch = process(model, imgs, args.sampler, args.steps, streams, args.guidance_scale, [ctx],
-                                       micro_batch_size=args.micro_batch_size or None,
+            preds, bpp_batch = process(model, imgs, args.sampler, args.steps, streams, args.guidance_scale, c_crossattn,
+                                       uc_crossattn=uc_crossattn, micro_batch_size=args.micro_batch_size or None,
                                        seeds=[args.seed + order[f] for f in batch],
                                        profile_memory=args.profile_memory, save_intermediates=args.save_intermediates,
                                        intermediate_prefixes=prefixes, latent_format=args.latent_format)
             per_image = (time.time() - t0) / len(batch)
-            for f, pred, (orig, scaled, rel), prefix, bpp in zip(batch, preds, targets, prefixes, bpp_batch):
+            for k, (f, pred, (orig, scaled, rel), prefix, bpp) in enumerate(zip(batch, preds, targets, prefixes,
+                                                                               bpp_batch)):
                 m = meta[f]
                 out = Image.fromarray(pred[:m["scaled_h"], :m["scaled_w"], :])
                 up = args.enable_resize_guard and args.upsample_to_original and m["scale"] < 1.0
@@ -302,6 +340,8 @@ def main(argv=None) -> List[Dict]:
                 out.save(f"{prefix}.png")
                 vals = compute_metrics(np.array(out), orig if up else scaled, lpips_model)
                 records.append({"image": rel, "bpp": bpp, "scale": m["scale"], **vals})
+                if texts is not None:
+                    records[-1]["caption"] = texts[k]
                 bpps.append(bpp)
                 print(f"save to {prefix}.png, bpp {bpp:.3f}, PSNR {vals['psnr']:.2f}dB, SSIM {vals['ssim']:.4f}, "
                       f"LPIPS {vals['lpips']:.4f}, time {per_image:.2f}s")
@@ -310,7 +350,8 @@ def main(argv=None) -> List[Dict]:
     if records:
         path = os.path.join(args.output, "metrics.csv")
         with open(path, "w", newline="") as fh:
-            w = csv.DictWriter(fh, fieldnames=["image", "bpp", "scale", "psnr", "ssim", "ms_ssim", "lpips"])
+            w = csv.DictWriter(fh, fieldnames=["image", "bpp", "scale", "psnr", "ssim", "ms_ssim", "lpips"] +
+                               (["caption"] if captions is not None else []))
             w.writeheader()
             w.writerows(records)
         for k in ("psnr", "ssim", "ms_ssim", "lpips"):

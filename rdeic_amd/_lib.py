@@ -93,6 +93,9 @@ PROTOTYPES = {
     "rdeic_transpose": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i64, _i32, _p]),
     "rdeic_attention": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f,
                                   _i32, _i32, _p]),
+    "rdeic_attention_causal": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _f, _i32,
+                                         _p]),
+    "rdeic_embed_tokens": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _i32, _p]),
     "rdeic_geglu": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _i32, _p]),
     "rdeic_nchw_to_nhwc": (C.c_int, [_p, _i32, _i32, _i32, _i32, _f, _f, _p, _i32, _i32, _p]),
     "rdeic_nhwc_to_nchw": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _f, _f, _p, _i32, _p]),

@@ -844,6 +844,27 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     return out
 
 
+def attention_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, batch: int, heads: int,
+                     l: int, dh: int, scale: float) -> torch.Tensor:
+    """Causal self-attention (key j <= query i) over [batch*l, heads*dh]-layout projections; dh must be 64
+    (the OpenCLIP text tower, rdeic_amd/text.py)."""
+    _launch(("attention_causal", 4.0 * batch * heads * dh * (l * (l + 1) / 2), None),
+            "rdeic_attention_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+            v.stride(0), out.data_ptr(), out.stride(0), batch, heads, l, dh, float(scale), dt_code(q), stream_ptr())
+    return out
+
+
+def embed_tokens(table: torch.Tensor, pos: torch.Tensor, tokens: torch.Tensor, dtype) -> torch.Tensor:
+    """[B, context] int32 device tokens -> [B*context, width] rows of table[tokens] + pos in `dtype` (fp32 tables).
+    The caller validates the ids against the table on the host."""
+    b, context = tokens.shape
+    width = table.shape[1]
+    out = torch.empty((b * context, width), dtype=dtype, device=table.device)
+    call("rdeic_embed_tokens", table.data_ptr(), table.stride(0), pos.data_ptr(), pos.stride(0), tokens.data_ptr(),
+         b, context, width, out.data_ptr(), out.stride(0), 1 if dtype == torch.bfloat16 else 0, stream_ptr())
+    return out
+
+
 # VAE AttnBlock in bf16 on the flash kernel (rdeic_attention, dh = 512); False: the materialised path
 VAE_FLASH_ATTENTION = True
 

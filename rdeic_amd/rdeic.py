@@ -6,11 +6,13 @@ API parity (model/rdeic.py, ldm/models/diffusion/ddpm.py):
   q_sample(x_start, t, noise)                                      ddpm.py:357-360
   apply_model(x_noisy, t, cond) -> eps                             rdeic.py:688-698
   decode_first_stage(z)                                            ddpm.py:835-844
+  get_learned_conditioning(c) -> text context                      encoders/modules.py:174-236
   alphas_cumprod & co. (register_schedule, ddpm.py:139-193), used_timesteps, parameterization,
   scale_factor, device, preprocess_model.update(force=True), load_state_dict(state_dict).
 Tensors crossing this API are the reference's NCHW fp32; internally everything is NHWC and the
 batched fast path (`codec_images`) never converts layouts between stages.
-Text conditioning (OpenCLIP, out of scope) is supplied as a context tensor [1 or B, 77, 1024].
+Text conditioning is a context tensor [1 or B, 77, 1024]: from get_learned_conditioning when the checkpoint
+holds the OpenCLIP text tower (rdeic_amd/text.py), else supplied by the caller (synthetic.synth_context).
 """
 from __future__ import annotations
 
@@ -70,6 +72,9 @@ class RDEIC:
         self.use_plans = True
         self._plans = PlanCache()
         self._consts = {}
+        # the OpenCLIP text tower (rdeic_amd/text.py): built by load_state_dict when the checkpoint holds it, or by
+        # init_text_synthetic; sessions share it (copy.copy keeps the reference)
+        self.cond_stage_model = None
 
     # ------------------------------------------------------------------ weights
     @property
@@ -85,10 +90,43 @@ class RDEIC:
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         """Load reference-named weights (e.g. a RDEIC checkpoint's state_dict). Non-parameter buffers of the
-        reference (schedules, entropy tables, scale_list, cond_stage_model) are ignored."""
+        reference (schedules, entropy tables, scale_list) are ignored. A dict that holds the frozen text tower
+        (`cond_stage_model.model.transformer.*`) also builds and loads `cond_stage_model`, whatever `strict` is;
+        one without those keys leaves it as it was."""
         self.store.load_state_dict({k: v for k, v in sd.items() if k in self.store.shapes}, strict=strict)
         self._clear_plans()
+        from . import text
+        if text.has_tower(sd):
+            # layer "penultimate": configs/model/rdeic.yaml:96-100
+            tower = text.OpenCLIPTextEncoder(text.TextConfig.from_state_dict(sd), self.compute_dtype, self.device)
+            self.cond_stage_model = tower.load_state_dict(sd)  # a new tower: the cached "" context goes with the old
         return self
+
+    def init_text_synthetic(self, cfg=None, seed: Optional[int] = None):
+        """A seeded synthetic text tower (tests and tools; rdeic_amd/text.py init_spec)."""
+        from . import text
+        self.cond_stage_model = text.OpenCLIPTextEncoder(cfg, self.compute_dtype, self.device).init_synthetic(seed)
+        return self
+
+    @torch.no_grad()
+    def get_learned_conditioning(self, c, vocab_path: Optional[str] = None) -> torch.Tensor:
+        """ddpm.py get_learned_conditioning -> FrozenOpenCLIPEmbedder.encode: c is a list of strings (tokenized by
+        rdeic_amd/tokenizer.py; non-empty texts need the BPE vocabulary) or an integer token tensor [B, 77].
+        Returns the text context [B, 77, 1024] on the device in the compute dtype. The context of [""] is
+        computed once per loaded tower."""
+        tower = self.cond_stage_model
+        if tower is None:
+            raise RuntimeError("no text tower loaded: the state dict held no cond_stage_model.model.transformer.* "
+                               "weights (load a full RDEIC checkpoint, or call init_text_synthetic)")
+        if isinstance(c, torch.Tensor):
+            return tower.encode_tokens(c)
+        if isinstance(c, str):
+            c = [c]
+        from . import tokenizer
+        c = list(c)
+        if len(c) == 1 and isinstance(c[0], str) and not tokenizer.clean(c[0]):
+            return tower.encode_empty()
+        return tower.encode_tokens(tokenizer.tokenize(c, vocab_path, context=tower.cfg.context))
 
     @property
     def use_plans(self) -> bool:
