@@ -264,6 +264,34 @@ int rdeic_pack_conv_weight(const float* w, int32_t cout, int32_t cin, int32_t kh
                            int32_t wld, int32_t dtype, void* stream);
 int rdeic_cast(const void* in, int32_t in_dtype, void* out, int32_t out_dtype, int64_t count, void* stream);
 
+/* ------------------------------------------- training-data image ops (image_ops.hip)
+ * The crop chain of the reference's dataset (utils/image/common.py:12-77: BOX halvings to (w//2, h//2),
+ * one BICUBIC resize, crop; :103-114: hflip, vflip, transpose) on uint8 HWC images, with the semantics of
+ * Pillow's 8-bit resampling (Resample.c): the caller computes precompute_coeffs / normalize_coeffs_8bpc on
+ * the host (device tables bounds[out_size][2] = (first tap, tap count) and kk[out_size][ksize], 22
+ * fractional bits) and a pass evaluates clip8((2^21 + sum_t kk[o][t] * px[bounds[o][0] + t]) >> 22) in
+ * int32, bit for bit what Image.resize gives. A resize is the horizontal pass, then the vertical one.
+ *
+ * vertical: rows are flat byte arrays of src_row_bytes bytes, src_stride bytes apart; `src` holds source
+ * rows src_row0 .. src_row0 + src_rows - 1. Produces output rows y0 .. y0+nrows-1 and byte columns
+ * cb0 .. cb0+ncb-1 into dst[(y - y0) * dst_stride + (col - cb0)]. */
+int rdeic_resample_v_u8(const uint8_t* src, int64_t src_stride, int32_t src_row_bytes, int32_t src_row0,
+                        int32_t src_rows, const int32_t* bounds, const int32_t* kk, int32_t ksize,
+                        int32_t out_size, int32_t y0, int32_t nrows, int32_t cb0, int32_t ncb, uint8_t* dst,
+                        int64_t dst_stride, void* stream);
+/* horizontal: src is [src_h][src_w][3] with rows src_stride bytes apart. Produces rows y0 .. y0+nrows-1
+ * and output pixels x0 .. x0+npix-1 into dst[(y - y0) * dst_stride + (x - x0) * 3 + c]. seg_max: the most
+ * source pixels any 64 consecutive output pixels read (sizes the LDS segment; -22 past 64 KiB). */
+int rdeic_resample_h_u8(const uint8_t* src, int64_t src_stride, int32_t src_h, int32_t src_w,
+                        const int32_t* bounds, const int32_t* kk, int32_t ksize, int32_t out_size,
+                        int32_t seg_max, int32_t y0, int32_t nrows, int32_t x0, int32_t npix, uint8_t* dst,
+                        int64_t dst_stride, void* stream);
+/* the h x w window at (crop_y, crop_x), then hflip, vflip, transpose in that order, into the dense
+ * [transpose ? w : h][transpose ? h : w][3] image at dst (one image's slot of a [B,S,S,3] batch) */
+int rdeic_crop_flip_u8(const uint8_t* src, int64_t src_stride, int32_t src_h, int32_t src_w, int32_t crop_y,
+                       int32_t crop_x, int32_t h, int32_t w, int32_t hflip, int32_t vflip, int32_t transpose,
+                       uint8_t* dst, void* stream);
+
 /* ---------------------------------------------------- entropy-model kernels
  * Checkerboard stage of slice `sl` (phase 0 = anchor, 1 = non-anchor) over a [n][hy][wy] latent.
  * params: [pix][pld] with scales at channel 0..c-1 and means at c..2c-1 (chunk(2,1)).

@@ -111,6 +111,12 @@ PROTOTYPES = {
     "rdeic_fill_uniform": (C.c_int, [_p, _i64, _u64, _f, _f, _p]),
     "rdeic_pack_conv_weight": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p]),
     "rdeic_cast": (C.c_int, [_p, _i32, _p, _i32, _i64, _p]),
+    # training-data image ops (image_ops.hip)
+    "rdeic_resample_v_u8": (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p,
+                                      _i64, _p]),
+    "rdeic_resample_h_u8": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p,
+                                      _i64, _p]),
+    "rdeic_crop_flip_u8": (C.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "rdeic_ckbd_encode": (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _f, _p, _p,
                                     _i64, _i64, _p, _i32, _p, _i32, _i32, _p]),
     "rdeic_ckbd_indexes": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _f, _p, _i64, _i64,

@@ -135,6 +135,27 @@ class FineTuner:
         self.buckets = GradBuckets(self.grad, params, bucket_bytes, group)
         return self.buckets
 
+    def sync_inference(self) -> None:
+        """Make the model's inference path (RDEIC.codec_images, the validation epochs) see the current trainable
+        parameters. The fp32 masters already are the flat buffer; what goes stale after a step are the packed
+        inference weights of trainable layers and everything derived from them: those packs are dropped (they
+        are packed again on first use), and so are the recorded launch plans that hold their pointers
+        (RDEIC._plans, Compression._plans), the codebook's cached row norms, and the entropy tables are rebuilt
+        (Compression.update(force=True)). The training state is left alone: the flat buffers, AG.PACKS /
+        AG.STEP_PACKS and a captured step's graph and pool stay valid, and frozen layers keep their packs."""
+        def trainable(key) -> bool:
+            for part in key:
+                names = part if isinstance(part, tuple) else (part,)
+                if any(isinstance(n, str) and n.startswith(TRAINABLE_PREFIXES) for n in names):
+                    return True
+            return False
+
+        st = self.m.store
+        for key in [k for k in st._packed if trainable(k)]:
+            del st._packed[key]
+        self.m._clear_plans()
+        self.m.preprocess_model.update(force=True)
+
     # ------------------------------------------------------------------ parameters
     def p(self, name: str) -> torch.Tensor:
         return self.m.store.t[name]

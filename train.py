@@ -3,8 +3,14 @@
   python train.py --config configs/finetune_ood.yaml [--max-steps N]
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py --config ...
 
-One process per GPU (RCCL): every rank trains on its own synthetic batches; gradients of the
+One process per GPU (RCCL): every rank trains on its own batches; gradients of the
 control model + compressor are all-reduced in buckets from the backward (FineTuner.enable_ddp).
+Data: with a `data.train` section (configs/finetune_ood_files.yaml, configs/refine_files.yaml; the reference's
+dataset / data_loader keys) batches come from an image file list through rdeic_amd/data.py (PIL decode on threads,
+the crop chain on the device), and a resumed run seeks the loader; without one, from a synthetic pool. With a
+`data.val` section and lightning.trainer.val_check_interval, a validation epoch (rdeic_amd/validate.py, the
+reference's model/rdeic.py:907-955) runs every that many steps and prints one JSON line (avg_bpp, usage, avg_psnr,
+avg_ssim, avg_ms_ssim); validation.save_images writes validation/{global_step}/{idx}.png under checkpoint.dirpath.
 Weights: random-init synthetic (rdeic_amd/weights.py) or `model.resume` (reference-named state
 dict, loaded with safe loaders only). With `is_refine: true` (configs/refine.yaml, the reference's
 configs/model/rdeic.yaml) the step is p_losses' refine branch: the relay sampler and the VAE decoder in the loop,
@@ -67,6 +73,27 @@ def save_checkpoint(ft, path: str, step: int) -> None:
     save_file(out, path, metadata={"global_step": str(step)})
 
 
+def make_loader(dc: dict, seed: int, rank: int, world: int, dev):
+    """An ImageListLoader from a data.train / data.val section (the reference's dataset.params and data_loader
+    keys; num_workers sizes the decode thread pool, 0 or absent: the cgroup share)."""
+    from rdeic_amd.data import ImageListLoader
+    return ImageListLoader(str(dc["file_list"]), int(dc["out_size"]), str(dc.get("crop_type", "center")),
+                           bool(dc.get("use_hflip", False)), bool(dc.get("use_rot", False)),
+                           int(dc.get("batch_size", 1)), bool(dc.get("shuffle", False)),
+                           bool(dc.get("drop_last", True)), seed, rank, world, dev,
+                           threads=int(dc.get("num_workers") or 0) or None,
+                           host_resize=bool(dc.get("host_resize", False)))
+
+
+def data_loaders(cfg: dict, seed: int, rank: int, world: int, dev):
+    """(train loader, validation loader) of the optional data.train / data.val sections; None for an absent one.
+    The validation list is not sharded by the loader (rank 0, world 1): the Validator shards it."""
+    dc = cfg.get("data") or {}
+    train = make_loader(dc["train"], seed, rank, world, dev) if dc.get("train") else None
+    val = make_loader(dc["val"], seed, 0, 1, dev) if dc.get("val") else None
+    return train, val
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "finetune_ood.yaml"))
@@ -118,9 +145,15 @@ def main(argv=None):
         ft.load_optimizer_state(sd["optimizer.exp_avg"], sd["optimizer.exp_avg_sq"], start)
     if world > 1:
         ft.enable_ddp()
-    S, B = int(dc["out_size"]), int(dc["batch_size"])
-    n_img = int(dc.get("n_images", 64))
-    pool = torch.from_numpy(np.stack([synth_image(S, S, seed + 1000 * rank + i) for i in range(n_img)])).to(dev)
+    loader, val_loader = data_loaders(cfg, seed, rank, world, dev)
+    if loader is not None:  # batches from image files; on resume the loader seeks, nothing is replayed
+        S, B = loader.out_size, loader.batch_size
+        loader.seek(start)
+        batches = loader.forever()
+    else:
+        S, B = int(dc["out_size"]), int(dc["batch_size"])
+        n_img = int(dc.get("n_images", 64))
+        pool = torch.from_numpy(np.stack([synth_image(S, S, seed + 1000 * rank + i) for i in range(n_img)])).to(dev)
     ctx = synth_context().to(dev)
     tr = lc["trainer"]
     max_steps = args.max_steps if args.max_steps is not None else int(tr["max_steps"])
@@ -130,17 +163,24 @@ def main(argv=None):
     ck_dir = ck.get("dirpath", "./logs/ood_finetune")
     slice_ch = model.cfg["compression"]["slice_ch"]
     rng = np.random.default_rng(seed + rank)
-    for _ in range(start):  # the batches the interrupted run already drew
+    for _ in range(start if loader is None else 0):  # the batches the interrupted run already drew
         rng.integers(0, n_img, size=B)
+    validator, val_every = None, int(tr.get("val_check_interval") or 0)
+    if val_loader is not None and val_every:  # validation epochs (model/rdeic.py:907-955) every val_check_interval steps
+        from rdeic_amd.validate import Validator
+        save = bool((cfg.get("validation") or {}).get("save_images", False))
+        validator = Validator(model, ft, val_loader, steps=ft.cfg.fixed_step if refine else 5, sampler="ddpm",
+                              lpips=lpips, save_dir=ck_dir if save else None, seed=seed,
+                              limit_batches=tr.get("limit_val_batches"), context=ctx)
     graph = None
     records = []
     t0 = time.perf_counter()
     for step in range(start + 1, max_steps + 1):
-        idx = rng.integers(0, n_img, size=B)
+        idx = rng.integers(0, n_img, size=B) if loader is None else None
         dseed = seed * 1000003 + step * 131 + rank
         dr = nchw_draws_to_nhwc(refine_draws(B, S // 8, S // 8, slice_ch, dseed, ft.cfg.fixed_step) if refine else
                                 train_draws(B, S // 8, S // 8, slice_ch, dseed, ft.cfg.used_timesteps), dev)
-        batch = pool[torch.from_numpy(idx).to(dev)]
+        batch = pool[torch.from_numpy(idx).to(dev)] if loader is None else next(batches)
         if world == 1 and not args.eager and not refine and graph is None:  # the refine step runs eagerly
             graph = CapturedStep(ft, batch, ctx, dr)  # one GPU: the step replays as one hipGraph
         d = graph.step(batch, dr) if graph is not None else ft.training_step(batch, ctx, dr)
@@ -152,6 +192,17 @@ def main(argv=None):
         if rank == 0 and ck_every and step % ck_every == 0:
             os.makedirs(ck_dir, exist_ok=True)
             save_checkpoint(ft, os.path.join(ck_dir, f"ood_finetune_step={step}.safetensors"), step)
+        if validator is not None and step % val_every == 0:  # every rank codes its shard of the list
+            vrec = validator.run(step)
+            if rank == 0:
+                vrec = {k: (round(v, 6) if isinstance(v, float) else v) for k, v in vrec.items()}
+                records.append(vrec)
+                print(json.dumps(vrec), flush=True)
+    if loader is not None:
+        batches.close()
+    for ld in (loader, val_loader):
+        if ld is not None:
+            ld.close()
     parallel.finish()
     return records
 
