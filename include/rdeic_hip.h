@@ -113,13 +113,25 @@ int rdeic_conv2d_splitk(const rdeic_conv_desc* d, int32_t splits, float* ws, siz
  * the bias is shared. The results differ from rdeic_conv2d's by the rounding of the folded weights only.
  * Eligible: bf16 in and out, c1 = 0, c0 % 64 == 0, out_mode 0, batch 1, no gn_ab / emb / res / ln_rows,
  * 16-byte-aligned rows. Images are launched in groups whose input and output spans stay below 2 GiB
- * (rdeic_conv2d_up2_group: images per group, 0 = one image is too large). gn_part as rdeic_conv2d (fused where
+ * (rdeic_conv2d_up2_group: images per group, 0 = one image is too large: it runs as row bands of whole source
+ * rows, rdeic_conv2d_band_rows). gn_part as rdeic_conv2d (fused where
  * h * w % 64 == 0: the partial of (image, phase, 64-row group g) is slot image * (4hw/64) + phase * (hw/64) + g).
  * tile: 25, 26, 30, 32, 33, 36 of rdeic_conv2d_tile, anything else = heuristic.
  * Returns 0, 1 = not eligible or switched off (rdeic_set_conv_option key 11; nothing was launched: run
  * rdeic_conv2d with the 3x3 weights), or a negative error. */
 int rdeic_conv2d_up2_phases(const rdeic_conv_desc* d, int64_t phase_stride, int32_t tile, void* stream);
 int rdeic_conv2d_up2_group(const rdeic_conv_desc* d);
+/* Row bands (host arithmetic only). The LDS-DMA, halo, phase and narrow kernels address activations through
+ * 32-bit byte offsets. A launch over several images past the launch limit (rdeic_set_conv_option key 12) runs as
+ * groups of whole images; ONE image past it runs as bands of output rows, each a launch of the same kernel on a
+ * row window of the input and of the output (out_mode 0, batch 1, bf16). Outputs and fused statistics are
+ * bit-identical to one launch, for any limit.
+ * Returns the output rows per band of d's image under the current limit: d->ho when the image fits, 0 when not
+ * even one row tile fits (the conv then takes its slower general kernel), else a multiple of row_tile (4 / 8:
+ * the halo kernels, 8: the narrow kernel, <= 1: the LDS-DMA tiles; 2 at least for up2) and, when d->gn_part is
+ * set, of whole 64-row statistic blocks (rows * wo % 64 == 0; up2: % 256, a block per phase). Every band's
+ * input, output and residual spans are <= the limit; the last band may be shorter. */
+int rdeic_conv2d_band_rows(const rdeic_conv_desc* d, int32_t row_tile);
 /* 2 (default): bf16 convs without a GN prologue pick among the big register-staged tiles
  * (256x256 / 256x128 / 128x256 / 128x128 / 64x128 / 128x64); 0: the 128-tile kernel with the
  * fused GroupNorm prologue everywhere (A/B timing, debugging). Results are bit-identical.
@@ -143,8 +155,10 @@ int rdeic_set_conv_path(int32_t path);
  *        (bit-identical to the register tile) and norm -> SiLU -> conv to <= 16 channels (fp32 rounding of the
  *        sums differs from the tiny-cout kernel): 1 on (default), 0 off.
  * key 11: rdeic_conv2d_up2_phases on (1, default) / off (0: it returns 1 and callers run the fused gather).
+ * key 12: the launch limit, the largest activation byte span one launch may address: default and maximum
+ *        2^31 - 1 (larger or non-positive values select it); image grouping and row banding both use it.
  * Returns the previous value, or -22 for an unknown key. Results are bit-identical either way
- * (keys 0-5; 6 and 8 change fp32 rounding only). */
+ * (keys 0-5 and 12; 6 and 8 change fp32 rounding only). */
 int rdeic_set_conv_option(int32_t key, int32_t value);
 
 /* --------------------------------------------------------- normalisation
@@ -461,7 +475,9 @@ int rdeic_prof_read_keys(int32_t kind, int64_t* keys, int64_t* launches, double*
 #define RDEIC_COUNT_SPLITK 5       /* rdeic_conv2d_splitk launches that ran split (partial pass + reduce) */
 #define RDEIC_COUNT_EDGE 6         /* the VAE edge convs (conv_edge.hip: conv_in from 8 channels, norm -> SiLU -> conv to <= 16) */
 #define RDEIC_COUNT_GN_PARTS_APPLY 7 /* rdeic_groupnorm_parts_apply (finalize + apply in one launch) */
-#define RDEIC_COUNT_KINDS 8
+#define RDEIC_COUNT_DMA_CONV 8 /* LDS-DMA conv launches (conv_dma.hip), the phase launches included: one per group / band */
+#define RDEIC_COUNT_UP2_PHASES 9 /* of those, the phase launches of rdeic_conv2d_up2_phases */
+#define RDEIC_COUNT_KINDS 10
 int64_t rdeic_launch_count(int32_t kind);
 /* Per-row LayerNorm statistics (attention.py:273-285, torch.nn.LayerNorm: biased variance, eps) of
  * bf16 rows x[rows][c] (pixel stride ld): ms[2 r] = mean, ms[2 r + 1] = 1 / sqrt(var + eps), two-pass

@@ -74,6 +74,7 @@ PROTOTYPES = {
     "rdeic_conv2d_tile": (C.c_int, [C.POINTER(ConvDesc), _i32, _p]),
     "rdeic_conv2d_up2_phases": (C.c_int, [C.POINTER(ConvDesc), _i64, _i32, _p]),
     "rdeic_conv2d_up2_group": (C.c_int, [C.POINTER(ConvDesc)]),
+    "rdeic_conv2d_band_rows": (C.c_int, [C.POINTER(ConvDesc), _i32]),
     "rdeic_prof_start": (C.c_int, [_i32, _i32]),
     "rdeic_prof_stop": (C.c_int, []),
     "rdeic_launch_count": (C.c_int64, [_i32]),

@@ -32,6 +32,7 @@ struct ConvArgs {
   int gn_hw;                 // pixels per image of the GroupNorm those statistics feed
   const float* ln_rows;      // folded LayerNorm: [M][2] (mean, rstd) of the raw input rows, or NULL
   const float* ln_cs;        // ... and the column sums of the packed (gamma-scaled) bf16 weight
+  int img_h;                 // phase launches: source rows of the whole image (h is the band's, see band_at)
 };
 
 // Folded LayerNorm (rdeic_conv_desc.ln_rows): LN(x) W = rstd (x W' - mean colsum(W')) with W' = diag(gamma) W
@@ -553,6 +554,22 @@ __device__ __forceinline__ void wait_vm_rt(int n) {
 
 // process-wide switches (rdeic_set_conv_option / rdeic_set_conv_path), defined in conv_gemm.hip
 extern int g_conv_path, g_epi_vec, g_swz, g_force_tile, g_dma, g_halo, g_halo8, g_edge, g_up2_phases;
+extern int g_launch_limit;  // largest byte span one launch addresses (rdeic_set_conv_option(12, v)), <= 2^31 - 1
+
+// ---- image groups and row bands (conv_dma.hip; host arithmetic) ----
+// The fast kernels address activations through 32-bit byte offsets. A launch over several images that exceeds
+// g_launch_limit runs as groups of whole images; one image that exceeds it runs as bands of output rows, each band
+// a launch of the same kernel over a row window of the input (h, pad_t) and of the output / residual (ho).
+long image_span(const rdeic_conv_desc* d);  // the largest of one image's input, output and residual byte spans
+// Output rows per band (a multiple of row_tile; with gn_part, of whole 64-row statistic blocks): ho when the image
+// fits, 0 when not even one row tile does.
+int band_rows(const rdeic_conv_desc* d, int row_tile);
+struct Band {
+  int r0, rows;   // output rows [r0, r0 + rows)
+  int i0, h;      // stored input rows [i0, i0 + h) the band reaches
+  int pad_t;      // rows of zero padding above input row i0 (0 for an interior band: it carries its upper rows)
+};
+Band band_at(const rdeic_conv_desc* d, int r0, int rows);
 
 // cross-unit entry points
 int make_args(const rdeic_conv_desc* d, ConvArgs& a, bool& vec);                                     // conv_gemm.hip

@@ -74,7 +74,8 @@ __device__ __forceinline__ void epilogue_scalar(const f32x4 (&acc)[TM][TN], cons
 // GEGLU epilogue's registers never count against the plain tiles
 // PH: the phase launch of a nearest-x2 upsample 3x3 conv (rdeic_conv2d_up2_phases). The tile id carries the
 // phase (a, b) between the M and the N tile index; the block runs the 2x2 conv of that phase over the raw
-// input (a.kh = a.kw = 2, a.up2 = 0, a.ho x a.wo = the source size; pad (1 - a, 1 - b); weights of the phase at
+// input (a.kh = a.kw = 2, a.up2 = 0, a.ho x a.wo = the source size; pad (a.pad_t - a, 1 - b) with a.pad_t = 1 for a
+// whole image and 0 for an interior row band, which carries its upper source row; weights of the phase at
 // a.w_bs elements per phase) and stores GEMM row (img, i, j) at output pixel (img, 2i + a, 2j + b) (PixPhase).
 template <int BM, int BN, int WGM, int WGN, int S, int EP, bool GEG = false, bool PH = false>
 __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned bytes0, unsigned bytes1,
@@ -122,7 +123,7 @@ __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned 
   if constexpr (PH) {  // the four phases of an M tile are neighbours on one XCD: they share the input through L2
     phase = mt & 3;
     mt >>= 2;
-    a.pad_t = 1 - (phase >> 1);
+    a.pad_t -= phase >> 1;
     a.pad_l = 1 - (phase & 1);
     a.weight += (long)phase * a.w_bs * 2;
   }
@@ -257,7 +258,7 @@ __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned 
 
   HALO_STAMP(2);
   if constexpr (PH) {
-    const PixPhase pm{a.h, a.w, phase >> 1, phase & 1};
+    const PixPhase pm{a.img_h, a.w, phase >> 1, phase & 1};
     if constexpr (TM % EP == 0 && (BM / EP) * (BN + 4) * 4 <= S * STAGE) {
       if (a.epi_vec && epi_vec_ok(a)) {
         epilogue_vec<BM, BN, WGM, WGN, NT, EP, RowsFrom, false, PixPhase>(acc, a, m0, n0, wm, wn, lane, tid, lds,
@@ -298,7 +299,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) __attribute__((amdgpu_num_sgpr(80))
   conv_dma_body<BM, BN, WGM, WGN, S, EP, GEG>(a, tiles_n, bytes0, bytes1, bytesw);
 }
 
-// DMA-path eligibility: bf16, 16-byte-aligned 64-channel blocks, every buffer < 2 GiB.
+// DMA-path eligibility: bf16, 16-byte-aligned 64-channel blocks, every input span inside the launch limit.
 bool dma_ok(const rdeic_conv_desc* d, const ConvArgs& a, unsigned& b0, unsigned& b1, unsigned& bw) {
   if (d->dtype != 1 || d->gn_ab || (d->c0 % 64) || (d->c1 % 64) || (d->ld0 % 8) || ((uintptr_t)d->in0 % 16)) return false;
   if (d->c1 && ((d->ld1 % 8) || ((uintptr_t)d->in1 % 16))) return false;
@@ -307,7 +308,7 @@ bool dma_ok(const rdeic_conv_desc* d, const ConvArgs& a, unsigned& b0, unsigned&
   const long e0 = ((pix - 1) * d->ld0 + d->c0) * 2 + (a.batch - 1) * d->in_bs * 2;
   const long e1 = d->c1 ? ((pix - 1) * d->ld1 + d->c1) * 2 : 16;
   const long ew = (long)d->cout * d->wld * 2 + (a.batch - 1) * d->w_bs * 2;
-  if (e0 >= (1l << 31) || e1 >= (1l << 31) || ew >= (1l << 31)) return false;
+  if (e0 > g_launch_limit || e1 > g_launch_limit || ew >= (1l << 31)) return false;
   if (a.batch > 1 && (d->in_bs % 8 || d->w_bs % 8)) return false;
   // batched operands are addressed from the per-z base: the descriptor covers one slice
   b0 = (unsigned)(((pix - 1) * d->ld0 + d->c0) * 2);
@@ -336,6 +337,7 @@ int launch_dma(ConvArgs a, unsigned b0, unsigned b1, unsigned bw, hipStream_t s,
     if (!ok) a.gn_part = nullptr;
     if (fused) *fused = ok;
   }
+  rdeic_count_launch(RDEIC_COUNT_DMA_CONV);
   const int tn = cdiv(a.cout, BN);
   const long tiles = (long)cdiv(a.M, BM) * tn;
   dim3 grid((unsigned)tiles, 1, a.splits > 1 ? a.splits : a.batch);
@@ -407,42 +409,135 @@ int launch_dma_auto(const ConvArgs& a, unsigned b0, unsigned b1, unsigned bw, hi
   }
 }
 
-// Images are independent in a conv, so a launch whose buffers exceed the 2 GiB reach of a
-// 32-bit buffer offset runs the DMA kernel over groups of images (same per-pixel arithmetic,
-// bit-identical). Returns -1 when the DMA path does not apply.
+// ---- image groups and row bands (conv_common.h) ----
+namespace {
+long gcd_l(long a, long b) { while (b) { const long t = a % b; a = b; b = t; } return a; }
+long lcm_l(long a, long b) { return a / gcd_l(a, b) * b; }
+// bytes of one stored input row / of one output row's pixels (the widest of the tensors addressed with them)
+long in_row_bytes(const rdeic_conv_desc* d) {
+  const long es = d->dtype == 0 ? 4 : 2;
+  const long ld = d->c1 && d->ld1 > d->ld0 ? d->ld1 : d->ld0;
+  return (long)d->w * ld * es;
+}
+long out_row_bytes(const rdeic_conv_desc* d) {
+  const long os = (d->out_f32 || d->dtype == 0) ? 4 : 2;
+  const long ld = d->res && d->res_ld > d->out_ld ? d->res_ld : d->out_ld;
+  return (d->out_mode == 1 ? 4l : 1l) * d->wo * ld * os;
+}
+}  // namespace
+
+long image_span(const rdeic_conv_desc* d) {
+  const long in = (long)d->h * in_row_bytes(d), out = (long)d->ho * out_row_bytes(d);
+  return in > out ? in : out;
+}
+
+int band_rows(const rdeic_conv_desc* d, int row_tile) {
+  if (d->h <= 0 || d->w <= 0 || d->ho <= 0 || d->wo <= 0 || d->ld0 <= 0 || d->out_ld <= 0) return 0;
+  const long lim = g_launch_limit;
+  if (image_span(d) <= lim) return d->ho;
+  const int kh = d->kh > 0 ? d->kh : 1, stride = d->stride > 0 ? d->stride : 1;
+  long step = row_tile > 1 ? row_tile : 1;
+  if (d->up2) step = lcm_l(step, 2);  // a band is whole source rows
+  if (d->gn_part) {                   // whole 64-row statistic blocks (up2: of each phase's source rows)
+    const long q = d->up2 ? 256 : 64;
+    step = lcm_l(step, q / gcd_l(d->wo, q));
+  }
+  // a band of r output rows reaches at most (r - 1) * stride + kh stored input rows (up2, 3x3: r / 2 + 2)
+  const long in_rows = lim / in_row_bytes(d);
+  long r = d->up2 ? 2 * (in_rows - 2) : (in_rows - kh) / stride + 1;
+  if (in_rows < (d->up2 ? 3 : kh)) r = 0;
+  const long by_out = lim / out_row_bytes(d);
+  if (by_out < r) r = by_out;
+  r = r / step * step;
+  if (r < step) return 0;
+  return (int)(r < d->ho ? r : d->ho);  // full bands from row 0, the last one shorter
+}
+
+Band band_at(const rdeic_conv_desc* d, int r0, int rows) {
+  Band b;
+  b.r0 = r0;
+  b.rows = d->ho - r0 < rows ? d->ho - r0 : rows;
+  if (d->up2) {  // the phase launch: source rows [r0 / 2, (r0 + rows) / 2) and one row above and below
+    const int s0 = r0 / 2, ns = b.rows / 2;
+    b.i0 = s0 > 0 ? s0 - 1 : 0;
+    b.pad_t = 1 - (s0 - b.i0);
+    const int i1 = s0 + ns + 1 < d->h ? s0 + ns + 1 : d->h;
+    b.h = i1 - b.i0;
+    return b;
+  }
+  const int top = r0 * d->stride - d->pad_t;  // input row of the band's first tap row
+  b.i0 = top > 0 ? top : 0;
+  b.pad_t = b.i0 - top;
+  const int end = (r0 + b.rows - 1) * d->stride - d->pad_t + d->kh;
+  b.h = (end < d->h ? end : d->h) - b.i0;
+  return b;
+}
+
+// Images are independent in a conv, and so are output rows: a launch whose spans exceed the launch limit (the
+// 2 GiB reach of a 32-bit buffer offset) runs the DMA kernel over groups of images, or, where one image exceeds
+// it, over row bands of each image (out_mode 0, batch 1; same per-pixel arithmetic, bit-identical).
+// Returns -1 when the DMA path does not apply.
 int dma_grouped(const rdeic_conv_desc* d, int tile, hipStream_t s, bool* fused) {
   ConvArgs a;
   bool vec = false;
   if (make_args(d, a, vec) != RDEIC_OK || !vec) return -1;
   unsigned b0, b1, bw;
-  if (dma_ok(d, a, b0, b1, bw)) return launch_dma_auto(a, b0, b1, bw, s, tile, d->gn_hw, fused);
-  if (d->batch > 1 || d->n <= 1) return -1;
-  // per-image sizes (bytes); pick the largest image group that fits
+  const bool whole = dma_ok(d, a, b0, b1, bw);
+  const long lim = g_launch_limit;
+  const long per = image_span(d);
+  if (whole && (d->batch > 1 || per * d->n <= lim)) return launch_dma_auto(a, b0, b1, bw, s, tile, d->gn_hw, fused);
+  if (d->batch > 1) return -1;
+  const int osz = (d->out_f32 || d->dtype == 0) ? 4 : 2;
   const long ipix = (long)d->h * d->w;
   const long per0 = ipix * d->ld0 * 2, per1 = d->c1 ? ipix * d->ld1 * 2 : 0;
-  const long per = per0 > per1 ? per0 : per1;
-  const int g = (int)(((1l << 31) - 1) / per);
-  if (g < 1) return -1;
-  rdeic_conv_desc e = *d;
-  const int osz = (d->out_f32 || d->dtype == 0) ? 4 : 2;
-  const long opix = d->out_mode == 1 ? 4l * d->ho * d->wo : (long)d->ho * d->wo;
-  for (int i0 = 0; i0 < d->n; i0 += g) {
-    e.n = d->n - i0 < g ? d->n - i0 : g;
-    e.in0 = (const char*)d->in0 + i0 * per0;
-    e.in1 = d->in1 ? (const char*)d->in1 + i0 * per1 : nullptr;
-    e.out = (char*)d->out + i0 * opix * d->out_ld * osz;
-    e.res = d->res ? (const char*)d->res + i0 * opix * d->res_ld * osz : nullptr;
-    e.emb = d->emb ? d->emb + (long)i0 * d->emb_ld : nullptr;
-    e.ln_rows = d->ln_rows ? d->ln_rows + 2l * i0 * d->ho * d->wo : nullptr;
-    ConvArgs ea;
-    if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return -1;
-    ea.gn_row0 = i0 * d->ho * d->wo;
-    bool f = false;
-    const int rc = launch_dma_auto(ea, b0, b1, bw, s, tile, d->gn_hw, &f);
-    if (rc != RDEIC_OK) return rc;
-    if (fused) *fused = (i0 == 0 ? f : (*fused && f));
+  if (per <= lim && d->n > 1) {  // the largest image group that fits
+    const int g = (int)(lim / per);
+    rdeic_conv_desc e = *d;
+    const long opix = d->out_mode == 1 ? 4l * d->ho * d->wo : (long)d->ho * d->wo;
+    for (int i0 = 0; i0 < d->n; i0 += g) {
+      e.n = d->n - i0 < g ? d->n - i0 : g;
+      e.in0 = (const char*)d->in0 + i0 * per0;
+      e.in1 = d->in1 ? (const char*)d->in1 + i0 * per1 : nullptr;
+      e.out = (char*)d->out + i0 * opix * d->out_ld * osz;
+      e.res = d->res ? (const char*)d->res + i0 * opix * d->res_ld * osz : nullptr;
+      e.emb = d->emb ? d->emb + (long)i0 * d->emb_ld : nullptr;
+      e.ln_rows = d->ln_rows ? d->ln_rows + 2l * i0 * d->ho * d->wo : nullptr;
+      ConvArgs ea;
+      if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return -1;
+      ea.gn_row0 = i0 * d->ho * d->wo;
+      bool f = false;
+      const int rc = launch_dma_auto(ea, b0, b1, bw, s, tile, d->gn_hw, &f);
+      if (rc != RDEIC_OK) return rc;
+      if (fused) *fused = (i0 == 0 ? f : (*fused && f));
+    }
+    return RDEIC_OK;  // *fused false if any group could not fuse: the caller recomputes the statistics
   }
-  return RDEIC_OK;  // *fused false if any group could not fuse: the caller recomputes the statistics
+  const int rows = (per > lim && d->out_mode == 0 && !d->up2 && d->dtype == 1) ? band_rows(d, 1) : 0;
+  if (rows <= 0 || rows >= d->ho) return whole ? launch_dma_auto(a, b0, b1, bw, s, tile, d->gn_hw, fused) : -1;
+  rdeic_conv_desc e = *d;
+  e.n = 1;
+  bool first = true;
+  for (int img = 0; img < d->n; ++img)
+    for (int r0 = 0; r0 < d->ho; r0 += rows) {
+      const Band b = band_at(d, r0, rows);
+      const long orow = ((long)img * d->ho + r0) * d->wo;  // first output pixel of the band
+      e.h = b.h; e.ho = b.rows; e.pad_t = b.pad_t;
+      e.in0 = (const char*)d->in0 + img * per0 + (long)b.i0 * d->w * d->ld0 * 2;
+      e.in1 = d->in1 ? (const char*)d->in1 + img * per1 + (long)b.i0 * d->w * d->ld1 * 2 : nullptr;
+      e.out = (char*)d->out + orow * d->out_ld * osz;
+      e.res = d->res ? (const char*)d->res + orow * d->res_ld * osz : nullptr;
+      e.emb = d->emb ? d->emb + (long)img * d->emb_ld : nullptr;
+      e.ln_rows = d->ln_rows ? d->ln_rows + 2 * orow : nullptr;
+      ConvArgs ea;
+      if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return first ? -1 : RDEIC_EINVAL;
+      ea.gn_row0 = (int)orow;
+      bool f = false;
+      const int rc = launch_dma_auto(ea, b0, b1, bw, s, tile, d->gn_hw, &f);
+      if (rc != RDEIC_OK) return rc;
+      if (fused) *fused = (first ? f : (*fused && f));
+      first = false;
+    }
+  return RDEIC_OK;
 }
 
 // ---- nearest-x2 upsample 3x3 conv as four folded 2x2 phase convs (rdeic_conv2d_up2_phases) ----
@@ -453,11 +548,13 @@ namespace {
 template <int BM, int BN, int WGM, int WGN, int S, int EP>
 int launch_dma_ph(ConvArgs a, unsigned b0, unsigned b1, unsigned bw, hipStream_t s, bool* fused) {
   if (a.gn_part) {
-    const bool ok = (a.h * a.w) % 64 == 0 && stats_tile_ok<BM, BN, WGM, WGM * WGN * 64, EP>() &&
+    const bool ok = (a.img_h * a.w) % 64 == 0 && (a.ho * a.wo) % 64 == 0 && stats_tile_ok<BM, BN, WGM, WGM * WGN * 64, EP>() &&
                     dma_vec_epilogue<BM, BN, WGM, WGN, S, EP>(a);
     if (!ok) a.gn_part = nullptr;
     if (fused) *fused = ok;
   }
+  rdeic_count_launch(RDEIC_COUNT_DMA_CONV);
+  rdeic_count_launch(RDEIC_COUNT_UP2_PHASES);
   const int tn = cdiv(a.cout, BN);
   const long tiles = (long)cdiv(a.M, BM) * 4 * tn;
   constexpr int lds = S * (BM + BN) * 128;
@@ -487,12 +584,12 @@ int launch_ph_auto(const ConvArgs& a, unsigned b0, unsigned b1, unsigned bw, hip
 }  // namespace
 
 // Images per launch of the phase path: the largest group whose input span and (4x larger) output span both stay
-// below 2 GiB, evened out over the groups; 0 when one image already exceeds that.
+// inside the launch limit, evened out over the groups; 0 when one image already exceeds that (it runs as row bands).
 int up2_phase_group(const rdeic_conv_desc* d) {
   const long ipix = (long)d->h * d->w;
   const long per_in = ipix * d->ld0 * 2, per_out = 4 * ipix * d->out_ld * 2;
   const long per = per_in > per_out ? per_in : per_out;
-  const long lim = (1l << 31) - 1;
+  const long lim = g_launch_limit;
   if (d->n <= 0 || per <= 0 || per > lim) return 0;
   long g = lim / per;
   if (g > d->n) g = d->n;
@@ -511,7 +608,7 @@ bool up2_phases_ok(const rdeic_conv_desc* d, long phase_stride) {
   if (d->ld0 < d->c0 || d->ld0 % 8 || ((uintptr_t)d->in0 % 16) || ((uintptr_t)d->weight % 16)) return false;
   if (d->cout % 8 || d->out_ld < d->cout || d->out_ld % 8 || ((uintptr_t)d->out % 16)) return false;
   if ((long)d->cout * d->wld * 2 >= (1l << 31)) return false;
-  return up2_phase_group(d) > 0;
+  return up2_phase_group(d) > 0 || band_rows(d, 1) > 0;
 }
 
 // -1: not eligible (nothing launched; the caller runs the fused-gather path)
@@ -522,6 +619,32 @@ int launch_up2_phases(const rdeic_conv_desc* d, long phase_stride, int tile, hip
   const long per_in = ipix * d->ld0 * 2, per_out = 4 * ipix * d->out_ld * 2;
   rdeic_conv_desc e = *d;  // one phase: the 2x2 conv over the raw input, h x w GEMM rows per image
   e.up2 = 0; e.kh = 2; e.kw = 2; e.stride = 1; e.pad_t = 1; e.pad_l = 1; e.ho = d->h; e.wo = d->w;
+  if (g == 0) {  // one image is past the launch limit: row bands of each image (band_at: source-row windows)
+    const int rows = band_rows(d, 1);
+    if (rows <= 0) return -1;
+    e.n = 1;
+    bool first = true;
+    for (int img = 0; img < d->n; ++img)
+      for (int r0 = 0; r0 < d->ho; r0 += rows) {
+        const Band b = band_at(d, r0, rows);
+        e.h = b.h; e.ho = b.rows / 2; e.pad_t = b.pad_t;
+        e.in0 = (const char*)d->in0 + img * per_in + (long)b.i0 * d->w * d->ld0 * 2;
+        e.out = (char*)d->out + img * per_out + (long)r0 * d->wo * d->out_ld * 2;
+        ConvArgs ea;
+        bool vec = false;
+        unsigned b0, b1, bw;
+        if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return first ? -1 : RDEIC_EINVAL;
+        ea.w_bs = phase_stride;
+        ea.img_h = d->h;
+        ea.gn_row0 = (int)(img * ipix + (long)(r0 / 2) * d->w);
+        bool f = false;
+        const int rc = launch_ph_auto(ea, b0, b1, bw, s, tile, &f);
+        if (rc != RDEIC_OK) return rc;
+        if (fused) *fused = (first ? f : (*fused && f));
+        first = false;
+      }
+    return RDEIC_OK;
+  }
   for (int i0 = 0; i0 < d->n; i0 += g) {
     e.n = d->n - i0 < g ? d->n - i0 : g;
     e.in0 = (const char*)d->in0 + i0 * per_in;

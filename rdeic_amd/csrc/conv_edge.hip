@@ -207,7 +207,9 @@ __global__ __launch_bounds__(TR * 64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   sp /= tiles_x;
   const int ty = sp % tiles_y, img = sp / tiles_y;
   const int oy0 = ty * TR, ox0 = tx * NR_TC;
-  const int H = a.h, W = a.w, cin = a.c0;
+  // input rows H of this launch's view, its top padding PT (0 above an interior row band, which carries its
+  // neighbour rows) and output rows HO; one launch over whole images has H = HO, PT = 1 (launch_narrow)
+  const int H = a.h, HO = a.ho, PT = a.pad_t, W = a.w, cin = a.c0;
   const int lr = lane & 15, lq = lane >> 4;
   const int q = tid & 3;  // this thread's 16-byte chunk of every halo pixel it loads (NT % 4 == 0)
   const bf16* in = reinterpret_cast<const bf16*>(a.in0);
@@ -238,7 +240,7 @@ __global__ __launch_bounds__(TR * 64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   for (int k = 0; k < NR::IPT; ++k) {
     const int it = tid + k * NR::NT, hp = it >> 2;
     const int hr = hp / NR_HC, hc = hp - (hp / NR_HC) * NR_HC;
-    const int iy = oy0 - 1 + hr, ix = ox0 - 1 + hc;
+    const int iy = oy0 - PT + hr, ix = ox0 - 1 + hc;
     goff[k] = (it < NR::ITEMS && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
                   ? (unsigned)(((img * H + iy) * W + ix) * a.ld0 + 8 * q) * 2u : kOOB;
     loff[k] = it < NR::ITEMS ? hp * 64 + ((q ^ nr_sw(hp)) << 4) : -1;
@@ -314,7 +316,7 @@ __global__ __launch_bounds__(TR * 64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   // lane: output channel lr, pixels ox0 + 16 i + 4 lq + r of row oy0 + wave
   if (lr >= a.cout) return;
   const float bias = a.bias ? a.bias[lr] : 0.f;
-  const long row = (long)(img * H + oy0 + wave) * W + ox0;
+  const long row = (long)(img * HO + oy0 + wave) * W + ox0;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -333,18 +335,44 @@ __global__ __launch_bounds__(TR * 64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 int g_edge = 1;  // the edge kernels where they apply (rdeic_set_conv_option(10, v)): 1 on (default), 0 off
 
 namespace {
+// Image groups and row bands as launch_halo: every launch's input view (a 32-bit descriptor and offsets in the
+// kernel) and output view stay inside the launch limit.
 int launch_narrow(const rdeic_conv_desc* d, const ConvArgs& a, hipStream_t s) {
   constexpr int TR = 8;
   const int lds = Narrow<TR>::LDS + d->c0 * 8 + d->cout * 9 * d->c0 * 2;
   if (!(d->gn_ab && d->cout <= 16 && d->c0 % 32 == 0 && d->h % TR == 0 && d->w % NR_TC == 0 && lds <= 160 * 1024 &&
         !d->gn_part && !d->emb && ((uintptr_t)d->gn_ab) % 16 == 0))
     return -1;
-  rdeic_count_launch(RDEIC_COUNT_EDGE);
-  const int tx = d->w / NR_TC, ty = d->h / TR;
-  const dim3 g((unsigned)((long)d->n * ty * tx));
-  if (d->gn_silu) hipLaunchKernelGGL((conv3x3_gn_narrow_kernel<TR, true>), g, dim3(TR * 64), lds, s, a, tx, ty);
-  else hipLaunchKernelGGL((conv3x3_gn_narrow_kernel<TR, false>), g, dim3(TR * 64), lds, s, a, tx, ty);
-  return launch_status();
+  const long ipix = (long)d->h * d->w;
+  const long lim = g_launch_limit, per = image_span(d);
+  const int g = per <= lim ? (int)(lim / per) : 1;  // images per launch
+  int rows = d->ho;                                  // output rows per launch
+  if (per > lim) {
+    rows = band_rows(d, TR);
+    if (rows <= 0) return -1;
+  }
+  const int osz = a.out_f32 ? 4 : 2;
+  for (int i0 = 0; i0 < d->n; i0 += g)
+    for (int r0 = 0; r0 < d->ho; r0 += rows) {
+      const Band bd = band_at(d, r0, rows);
+      const long opix = i0 * ipix + (long)r0 * d->w;  // first output pixel of the launch
+      ConvArgs e = a;
+      e.n = d->n - i0 < g ? d->n - i0 : g;
+      e.h = bd.h; e.ho = bd.rows; e.pad_t = bd.pad_t;
+      e.M = e.n * e.ho * d->wo;
+      e.in0 = a.in0 + (i0 * ipix + (long)bd.i0 * d->w) * d->ld0 * 2;
+      e.out = a.out + opix * d->out_ld * osz;
+      e.res = a.res ? a.res + opix * d->res_ld * osz : nullptr;
+      e.gn_ab = a.gn_ab + (long)i0 * d->c0 * 2;
+      rdeic_count_launch(RDEIC_COUNT_EDGE);
+      const int tx = d->w / NR_TC, ty = e.ho / TR;
+      const dim3 gr((unsigned)((long)e.n * ty * tx));
+      if (d->gn_silu) hipLaunchKernelGGL((conv3x3_gn_narrow_kernel<TR, true>), gr, dim3(TR * 64), lds, s, e, tx, ty);
+      else hipLaunchKernelGGL((conv3x3_gn_narrow_kernel<TR, false>), gr, dim3(TR * 64), lds, s, e, tx, ty);
+      const int rc = launch_status();
+      if (rc != RDEIC_OK) return rc;
+    }
+  return RDEIC_OK;
 }
 }  // namespace
 
@@ -357,6 +385,8 @@ int launch_edge(const rdeic_conv_desc* d, const ConvArgs& a, hipStream_t s, bool
   // conv_in: 8 input channels, bias only, bf16 output, statistics per image (64-row blocks)
   if (d->c0 == 8 && !d->gn_ab && d->wld >= 128 && d->cout % 32 == 0 && d->cout <= 128 && d->w % 64 == 0 && !d->emb && !d->act && !d->res &&
       !d->out_f32 && !d->ln_rows && d->out_ld % 8 == 0 && ((uintptr_t)d->out) % 16 == 0) {
+    // 16 bytes per pixel: no bands; an input past the kernel's 32-bit descriptor takes the general path
+    if ((long)a.M * d->ld0 * 2 > g_launch_limit) return -1;
     ConvArgs e = a;
     const bool stats = e.gn_part != nullptr && e.gn_hw > 0 && e.gn_hw % 64 == 0;
     if (!stats) e.gn_part = nullptr;

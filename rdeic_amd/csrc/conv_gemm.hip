@@ -30,6 +30,7 @@ int g_dma = 1;          // LDS-DMA path for cin % 64 == 0 (rdeic_set_conv_option
 int g_halo = 1;         // 3x3 halo conv: 0 off, 1 for GroupNorm-input convs (default), 2 for every eligible conv
 int g_halo8 = 1;        // the 8-row halo conv where it applies (rdeic_set_conv_option(9, v))
 int g_up2_phases = 1;   // rdeic_conv2d_up2_phases runs the four folded 2x2 phase convs (rdeic_set_conv_option(11, v))
+int g_launch_limit = 0x7fffffff;  // largest activation byte span of one launch (rdeic_set_conv_option(12, v))
 
 namespace {
 
@@ -537,7 +538,7 @@ int make_args(const rdeic_conv_desc* d, ConvArgs& a, bool& vec) {
   if (d->dtype != 0 && d->dtype != 1) return RDEIC_EINVAL;
   a.in0 = (const char*)d->in0; a.in1 = (const char*)(d->in1 ? d->in1 : d->in0);
   a.c0 = d->c0; a.c1 = d->c1; a.ld0 = d->ld0; a.ld1 = d->c1 ? d->ld1 : d->ld0;
-  a.n = d->n; a.h = d->h; a.w = d->w; a.up2 = d->up2;
+  a.n = d->n; a.h = d->h; a.w = d->w; a.up2 = d->up2; a.img_h = d->h;
   a.weight = (const char*)d->weight; a.wld = d->wld; a.bias = d->bias;
   a.cout = d->cout; a.kh = d->kh; a.kw = d->kw; a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l;
   a.ho = d->ho; a.wo = d->wo;
@@ -812,6 +813,9 @@ extern "C" int rdeic_conv2d_up2_phases(const rdeic_conv_desc* d, int64_t phase_s
 // Images per launch of rdeic_conv2d_up2_phases for this descriptor (host arithmetic only).
 extern "C" int rdeic_conv2d_up2_group(const rdeic_conv_desc* d) { return d ? up2_phase_group(d) : 0; }
 
+// Output rows per band of this descriptor's image under the launch limit (host arithmetic only).
+extern "C" int rdeic_conv2d_band_rows(const rdeic_conv_desc* d, int32_t row_tile) { return d ? band_rows(d, row_tile) : 0; }
+
 extern "C" int rdeic_set_conv_path(int32_t path) {
   int prev = g_conv_path;
   g_conv_path = path;
@@ -832,5 +836,6 @@ extern "C" int rdeic_set_conv_option(int32_t key, int32_t value) {
   if (key == 9) { int prev = g_halo8; g_halo8 = value; return prev; }
   if (key == 10) { int prev = g_edge; g_edge = value; return prev; }
   if (key == 11) { int prev = g_up2_phases; g_up2_phases = value; return prev; }
+  if (key == 12) { int prev = g_launch_limit; g_launch_limit = value > 0 ? value : 0x7fffffff; return prev; }
   return RDEIC_EINVAL;
 }

@@ -222,7 +222,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   sp /= tiles_x;
   const int ty = sp % tiles_y, img = sp / tiles_y;
   const int oy0 = ty * TR, ox0 = tx * TC, n0 = nt * BN;
-  const int H = a.h, W = a.w, cin = a.c0;
+  // input rows H of this launch's view (a row band carries its neighbour rows: PT = 0 above an interior band, 1 =
+  // the image's zero padding) and output rows HO; one launch over whole images has H = HO, PT = 1
+  const int H = a.h, HO = a.ho, PT = a.pad_t, W = a.w, cin = a.c0;
   const int ncb = cin >> 5, U = ncb * 9;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     hvo[k] = kOOB;
     if (sl < HPIX) {
       const int hr = sl / HC, hc = sl - (sl / HC) * HC;
-      const int iy = oy0 - 1 + hr, ix = ox0 - 1 + hc;
+      const int iy = oy0 - PT + hr, ix = ox0 - 1 + hc;
       if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
         hvo[k] = (unsigned)((img * H + iy) * W + ix) * (unsigned)(a.ld0 * 2) + (unsigned)((ph ^ sw(sl)) * 16);
     }
@@ -252,7 +254,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // lane i of piece q brings pass row 4q + i / 16 (wave row (4q + i / 16) / 16), chunk i % 16
   const bool res_dma = FE && a.res != nullptr;
   const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(res_dma ? a.res : a.in0), (short)0, res_dma ? (int)((long)(img * H + H) * W * a.res_ld * 2) : 0, 0x00020000);
+      (void*)(res_dma ? a.res : a.in0), (short)0, res_dma ? (int)((long)(img * HO + HO) * W * a.res_ld * 2) : 0, 0x00020000);
   const int parity = (cin >> 5) & 1;
   // weight rows of this wave: n = 16 wave + lane / 4, chunk lane % 4
   unsigned bvo;
@@ -363,7 +365,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
       if (t == 0 && more) issue_halo(cb + 1);
       if (t == 7 && !more && res_dma)  // pass 0's residual rows into the halo buffer the last block does not read
-        halo_res_dma<NW>(rsr, lds + halo::res_off(parity, 0), (img * H + oy0) * W + ox0, W, a.res_ld, n0, wave, lane, 0);
+        halo_res_dma<NW>(rsr, lds + halo::res_off(parity, 0), (img * HO + oy0) * W + ox0, W, a.res_ld, n0, wave, lane, 0);
       const char* bb = bbuf + (t % NB) * BBYTES + (wn * 64 + lr) * 64 + bsw;
       const int ky = t / 3, kx = t - (t / 3) * 3;
       bf16x8 bfv[4];
@@ -394,14 +396,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   HALO_STAMP(2);
   if constexpr (FE) {
     if (a.res)
-      halo_epilogue<NW, true>(acc, a, n0, wm, wn, tid, lds, (img * H + oy0) * W + ox0, W, park_off(parity),
+      halo_epilogue<NW, true>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, park_off(parity),
                               res_off(parity, 0), res_off(parity, 1), rsr, wave);
     else
-      halo_epilogue<NW, false>(acc, a, n0, wm, wn, tid, lds, (img * H + oy0) * W + ox0, W, park_off(parity),
+      halo_epilogue<NW, false>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, park_off(parity),
                                res_off(parity, 0), res_off(parity, 1), rsr, wave);
   } else {
     epilogue_vec<TR * TC, BN, 4, 2, NT, 2, Rows, false>(acc, a, 0, n0, wm, wn, lane, tid, lds,
-                                                        Rows{(img * H + oy0) * W + ox0, W});
+                                                        Rows{(img * HO + oy0) * W + ox0, W});
   }
   HALO_STAMP(3);
 }
@@ -467,7 +469,9 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
   sp /= tiles_x;
   const int ty = sp % tiles_y, img = sp / tiles_y;
   const int oy0 = ty * TR, ox0 = tx * TC, n0 = nt * BN;
-  const int H = a.h, W = a.w, cin = a.c0;
+  // input rows H of this launch's view (a row band carries its neighbour rows: PT = 0 above an interior band, 1 =
+  // the image's zero padding) and output rows HO; one launch over whole images has H = HO, PT = 1
+  const int H = a.h, HO = a.ho, PT = a.pad_t, W = a.w, cin = a.c0;
   const int ncb = cin >> 5, U = ncb * 9;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -479,7 +483,7 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)a.weight, (short)0, (int)bytesw, 0x00020000);
   const bool res_dma = a.res != nullptr;
   const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(res_dma ? a.res : a.in0), (short)0, res_dma ? (int)((long)(img * H + H) * W * a.res_ld * 2) : 0, 0x00020000);
+      (void*)(res_dma ? a.res : a.in0), (short)0, res_dma ? (int)((long)(img * HO + HO) * W * a.res_ld * 2) : 0, 0x00020000);
   const int f = ncb & 1;  // the halo buffer the last channel block does not read
 
   // halo waves: pieces hw + 8 k (k < 6; past the 42 pieces, piece hw + 32 again: same bytes, same slots).
@@ -492,7 +496,7 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
     unsigned vo = kOOB;
     if (sl < HPIX) {
       const int hr = sl / HC, hc = sl - (sl / HC) * HC;
-      const int iy = oy0 - 1 + hr, ix = ox0 - 1 + hc;
+      const int iy = oy0 - PT + hr, ix = ox0 - 1 + hc;
       if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
         vo = (unsigned)((img * H + iy) * W + ix) * (unsigned)(a.ld0 * 2) + (unsigned)((ph ^ sw(sl)) * 16);
     }
@@ -510,7 +514,7 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
     bool in = false;
     if (p < NPIECE && sl < HPIX) {
       const int hr = sl / HC, hc = sl - (sl / HC) * HC;
-      const int iy = oy0 - 1 + hr, ix = ox0 - 1 + hc;
+      const int iy = oy0 - PT + hr, ix = ox0 - 1 + hc;
       in = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
     }
     if (in) tinfo |= 1u << k;
@@ -628,7 +632,7 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
       if (t == 0 && !more && res_dma && !wload) {
         int l = lane;
         asm volatile("" : "+v"(l));
-        const int base = (img * H + oy0) * W + ox0;
+        const int base = (img * HO + oy0) * W + ox0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int q = hw + 8 * k, pr = 4 * q + (l >> 4);
@@ -662,10 +666,10 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
   }
   HALO_STAMP(2);
   if (a.res)
-    halo_epilogue<NW, true>(acc, a, n0, wm, wn, tid, lds, (img * H + oy0) * W + ox0, W, park_off(f), res_off(f, 0),
+    halo_epilogue<NW, true>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, park_off(f), res_off(f, 0),
                             res_off(f, 1), rsr, wave);
   else
-    halo_epilogue<NW, false>(acc, a, n0, wm, wn, tid, lds, (img * H + oy0) * W + ox0, W, park_off(f), res_off(f, 0),
+    halo_epilogue<NW, false>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, park_off(f), res_off(f, 0),
                              res_off(f, 1), rsr, wave);
   HALO_STAMP(3);
 }
@@ -677,34 +681,47 @@ bool halo_ok(const rdeic_conv_desc* d, const ConvArgs& a) {
          d->ld0 % 8 == 0 && ((uintptr_t)d->in0 % 16) == 0 && d->wld % 64 == 0 && epi_vec_ok(a) && a.epi_vec;
 }
 
-// The halo conv over image groups whose input stays inside a 32-bit buffer offset.
+// The halo conv over image groups whose spans stay inside the launch limit (32-bit buffer offsets), or, where one
+// image exceeds it, over row bands of each image: the same kernel on a row window of the input (band_at: an
+// interior band carries its neighbour rows, only the image's own borders read the zero padding) and of the
+// output / residual. Bit-identical to one launch; -1 when not even one row tile fits.
 int launch_halo(const rdeic_conv_desc* d, ConvArgs a, hipStream_t s, bool* fused) {
   using namespace halo;
   const long ipix = (long)d->h * d->w;
-  const long per = ipix * d->ld0 * 2;
-  const int g = (int)(((1l << 31) - 1) / per);
-  if (g < 1 || (long)d->cout * d->wld * 2 >= (1l << 31)) return -1;
+  const long lim = g_launch_limit, per = image_span(d);
+  if ((long)d->cout * d->wld * 2 >= (1l << 31)) return -1;
+  const bool fe = !a.out_f32 && !a.emb && a.act == 0;
+  const bool h8 = g_halo8 && fe && d->h % halo8::TR == 0;  // the 8-row, one-block-per-CU form
+  const int g = per <= lim ? (int)(lim / per) : 1;  // images per launch
+  int rows = d->ho;                                  // output rows per launch
+  if (per > lim) {
+    rows = band_rows(d, h8 ? halo8::TR : TR);
+    if (rows <= 0) return -1;
+  }
   const bool stats = a.gn_part != nullptr && d->gn_hw == ipix;
   if (fused) *fused = stats;
   if (!stats) a.gn_part = nullptr;
   const int osz = a.out_f32 ? 4 : 2;
-  for (int i0 = 0; i0 < d->n; i0 += g) {
+  for (int i0 = 0; i0 < d->n; i0 += g)
+  for (int r0 = 0; r0 < d->ho; r0 += rows) {
+    const Band bd = band_at(d, r0, rows);
+    const long opix = i0 * ipix + (long)r0 * d->w;  // first output pixel of the launch
     ConvArgs e = a;
     e.n = d->n - i0 < g ? d->n - i0 : g;
-    e.M = e.n * d->ho * d->wo;
-    e.in0 = a.in0 + i0 * per;
-    e.out = a.out + i0 * ipix * d->out_ld * osz;
-    e.res = a.res ? a.res + i0 * ipix * d->res_ld * osz : nullptr;
+    e.h = bd.h; e.ho = bd.rows; e.pad_t = bd.pad_t;
+    e.M = e.n * e.ho * d->wo;
+    e.in0 = a.in0 + (i0 * ipix + (long)bd.i0 * d->w) * d->ld0 * 2;
+    e.out = a.out + opix * d->out_ld * osz;
+    e.res = a.res ? a.res + opix * d->res_ld * osz : nullptr;
     e.emb = a.emb ? a.emb + (long)i0 * a.emb_ld : nullptr;
     e.gn_ab = a.gn_ab ? a.gn_ab + (long)i0 * d->c0 * 2 : nullptr;
-    e.gn_row0 = i0 * (int)ipix;
-    const unsigned b0 = (unsigned)(((e.n * ipix - 1) * d->ld0 + d->c0) * 2);
+    e.gn_row0 = (int)opix;
+    const unsigned b0 = (unsigned)((((long)e.n * e.h * d->w - 1) * d->ld0 + d->c0) * 2);
     const unsigned bw = (unsigned)((long)d->cout * d->wld * 2);
     rdeic_count_launch(RDEIC_COUNT_HALO_CONV);
-    const bool fe = !e.out_f32 && !e.emb && e.act == 0;
     const int gm = e.gn_ab ? (e.gn_silu ? 2 : 1) : 0;
-    if (g_halo8 && fe && d->h % halo8::TR == 0) {  // the 8-row, one-block-per-CU form
-      const int tx8 = d->w / halo8::TC, ty8 = d->h / halo8::TR;
+    if (h8) {
+      const int tx8 = d->w / halo8::TC, ty8 = e.ho / halo8::TR;
       const dim3 g8((unsigned)((long)e.n * ty8 * tx8 * (d->cout / halo8::BN))), b8(halo8::NT);
       if (gm == 2) hipLaunchKernelGGL((conv3x3_halo8_kernel<2>), g8, b8, halo8::LDS, s, e, tx8, ty8, b0, bw);
       else if (gm == 1) hipLaunchKernelGGL((conv3x3_halo8_kernel<1>), g8, b8, halo8::LDS, s, e, tx8, ty8, b0, bw);
@@ -713,15 +730,15 @@ int launch_halo(const rdeic_conv_desc* d, ConvArgs a, hipStream_t s, bool* fused
       if (rc != RDEIC_OK) return rc;
       continue;
     }
-    const int tx = d->w / TC, ty = d->h / TR;
+    const int tx = d->w / TC, ty = e.ho / TR;
     const long tiles = (long)e.n * ty * tx * (d->cout / BN);
-    const dim3 g((unsigned)tiles), b(NT);
-    if (gm == 2 && fe) hipLaunchKernelGGL((conv3x3_halo_kernel<2, true>), g, b, LDS, s, e, tx, ty, b0, bw);
-    else if (gm == 2) hipLaunchKernelGGL((conv3x3_halo_kernel<2, false>), g, b, LDS, s, e, tx, ty, b0, bw);
-    else if (gm == 1 && fe) hipLaunchKernelGGL((conv3x3_halo_kernel<1, true>), g, b, LDS, s, e, tx, ty, b0, bw);
-    else if (gm == 1) hipLaunchKernelGGL((conv3x3_halo_kernel<1, false>), g, b, LDS, s, e, tx, ty, b0, bw);
-    else if (fe) hipLaunchKernelGGL((conv3x3_halo_kernel<0, true>), g, b, LDS, s, e, tx, ty, b0, bw);
-    else hipLaunchKernelGGL((conv3x3_halo_kernel<0, false>), g, b, LDS, s, e, tx, ty, b0, bw);
+    const dim3 gr((unsigned)tiles), b(NT);
+    if (gm == 2 && fe) hipLaunchKernelGGL((conv3x3_halo_kernel<2, true>), gr, b, LDS, s, e, tx, ty, b0, bw);
+    else if (gm == 2) hipLaunchKernelGGL((conv3x3_halo_kernel<2, false>), gr, b, LDS, s, e, tx, ty, b0, bw);
+    else if (gm == 1 && fe) hipLaunchKernelGGL((conv3x3_halo_kernel<1, true>), gr, b, LDS, s, e, tx, ty, b0, bw);
+    else if (gm == 1) hipLaunchKernelGGL((conv3x3_halo_kernel<1, false>), gr, b, LDS, s, e, tx, ty, b0, bw);
+    else if (fe) hipLaunchKernelGGL((conv3x3_halo_kernel<0, true>), gr, b, LDS, s, e, tx, ty, b0, bw);
+    else hipLaunchKernelGGL((conv3x3_halo_kernel<0, false>), gr, b, LDS, s, e, tx, ty, b0, bw);
     const int rc = launch_status();
     if (rc != RDEIC_OK) return rc;
   }

@@ -581,8 +581,32 @@ def set_conv_path(path: int) -> int:
 def set_conv_option(key: int, value: int) -> int:
     """rdeic_set_conv_option (include/rdeic_hip.h): 0 vector epilogue, 1 dh=64 attention kernel, 3 swizzle,
     4 forced register tile, 5 LDS-DMA path, 6 halo conv, 8 d=512 attention form, 9 8-row halo conv, 10 VAE edge
-    convs, 11 the phase launch of the nearest-x2 upsample convs."""
+    convs, 11 the phase launch of the nearest-x2 upsample convs, 12 the launch limit (set_launch_limit)."""
     return int(_lib.load().rdeic_set_conv_option(int(key), int(value)))
+
+
+LAUNCH_LIMIT_MAX = 2 ** 31 - 1  # the reach of the fast conv kernels' 32-bit byte offsets
+
+
+def set_launch_limit(nbytes: int) -> int:
+    """The largest activation byte span one fast conv launch may address (rdeic_set_conv_option(12, .)); default and
+    maximum 2^31 - 1, larger values are clamped to it. Launches past it run as image groups, one image past it as
+    row bands of the same kernel (rdeic_conv2d_band_rows); results do not depend on it. Returns the previous."""
+    return set_conv_option(12, max(1, min(int(nbytes), LAUNCH_LIMIT_MAX)))
+
+
+def _band_plan_ok(x: torch.Tensor, p: "ConvParams", out, row_tile: int) -> bool:
+    """Whether the library's band planner (rdeic_conv2d_band_rows) has a plan for this 3x3 / stride-1 / pad-1 conv
+    under the launch limit: the whole image, or bands of row_tile rows; False = not even one row tile fits and the
+    halo / narrow kernels do not take the launch."""
+    n, h, w, _ = x.shape
+    d = ConvDesc()
+    d.n, d.h, d.w, d.ho, d.wo = n, h, w, h, w
+    d.c0, d.ld0, d.cout = x.shape[3], pix_ld(x), p.cout
+    d.kh, d.kw, d.stride, d.pad_t, d.pad_l = 3, 3, 1, 1, 1
+    d.out_ld = pix_ld(out) if out is not None else p.cout
+    d.dtype = 1
+    return int(_lib.load().rdeic_conv2d_band_rows(C.byref(d), row_tile)) > 0
 
 
 # 3x3 halo conv (rdeic_amd/csrc/conv_halo.hip, conv3x3_halo8_kernel / conv3x3_halo_kernel): a conv whose input is a
@@ -599,7 +623,7 @@ HALO_MAX_C = 512
 
 # launch counters of the library (rdeic_launch_count, RDEIC_COUNT_* in include/rdeic_hip.h)
 COUNT_HALO_CONV, COUNT_GN_APPLY, COUNT_LAYERNORM, COUNT_HALO_SMALL, COUNT_LN_FUSED, COUNT_SPLITK, COUNT_EDGE, \
-    COUNT_GN_PARTS_APPLY = 0, 1, 2, 3, 4, 5, 6, 7
+    COUNT_GN_PARTS_APPLY, COUNT_DMA_CONV, COUNT_UP2_PHASES = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 
 
 def set_up2_phases(on: bool) -> bool:
@@ -642,7 +666,7 @@ def _halo_eligible(x, x2, p: "ConvParams", up2, pad_t, pad_l, out_hw, special, o
         return False
     if out is not None and (pix_ld(out) % 8 or out.data_ptr() % 16):
         return False
-    return True
+    return _band_plan_ok(x, p, out, 8 if h % 8 == 0 else 4)
 
 
 # The VAE edge convs (rdeic_amd/csrc/conv_edge.hip, rdeic_set_conv_option(10, .)): conv_in from 8 channels on
@@ -671,7 +695,7 @@ def _edge_narrow_eligible(x, x2, p: "ConvParams", up2, pad_t, pad_l, out_hw, spe
         return False
     lds = 10 * 66 * 64 + c * 8 + p.cout * 9 * c * 2  # 8-row halo, GroupNorm table, weights (conv_edge.hip)
     return p.cout <= 16 and c % 32 == 0 and lds <= 160 * 1024 and h % 8 == 0 and w % 64 == 0 \
-        and x.stride(2) % 8 == 0 and x.data_ptr() % 16 == 0
+        and x.stride(2) % 8 == 0 and x.data_ptr() % 16 == 0 and _band_plan_ok(x, p, None, 8)
 
 
 def _gn_materialize(x: torch.Tensor, x2: Optional[torch.Tensor], p: ConvParams) -> bool:
