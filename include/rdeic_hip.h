@@ -348,6 +348,25 @@ size_t rdeic_image_ssim_ws_floats(int32_t n, int32_t h, int32_t w, int32_t level
 int rdeic_image_ssim(const uint8_t* a, const uint8_t* b, int32_t n, int32_t h, int32_t w, int32_t levels, float* ws,
                      size_t ws_floats, float* out, void* stream);
 
+/* ------------------------------------------- no-reference image quality (nr_metrics.hip)
+ * The device passes of NIQE / BRISQUE (the reference's pyiqa "niqe" / "brisque", experiments/run_ood.py:93-127;
+ * restated from the published algorithms, parity unpinned) on uint8 RGB [n][h][w][3]; the host fits the AGGD
+ * parameters from the moments (rdeic_amd/metrics.py). Per image and scale s = 0, 1: Y = rint(255 * YIQ luma) of
+ * the top-left hc x wc crop; MSCN M = (Y - mu) / (sigma + 1) with the separable 7x7 Gaussian (sigma 7/6, replicate
+ * border at the crop's edge; a constant image gives M == 0 exactly); scale 1 on the half-size plane of the
+ * un-normalised Y (8-tap [-3 -9 29 111 111 29 -9 -3] / 256 on inputs 2i-3 .. 2i+4, symmetric reflection, vertical
+ * pass then horizontal); then per region and per map (M, and M * roll(M, d) for d = (0,1), (1,0), (1,1), (1,-1),
+ * the roll circular within the region) the six moments (n_neg, n_pos, sum x^2 | x<0, sum x^2 | x>0, sum |x|,
+ * sum x^2). block = 96: hc, wc = the multiples of 96 below h, w, regions = the 96x96 blocks (48x48 at scale 1),
+ * row-major; block = 0: hc, wc = h, w (even, >= 8), one region, the whole plane. Any other block, or no region:
+ * -22 (ws_floats: 0). out_scale0 / out_scale1: fp64 [n][regions][5][6]. Row bands of a region write fp32 partials
+ * that are added in band order in fp64: no atomics, bit-identical from run to run.
+ * ws (fp32, rdeic_nr_moments_ws_floats floats) holds afterwards, with P = hc * wc: Y of scale 0 [n][hc][wc] at 0,
+ * M of scale 0 at n*P, the half-size plane [n][hc/2][wc/2] at 2*n*P, M of scale 1 at 2*n*P + n*P/4, then partials. */
+size_t rdeic_nr_moments_ws_floats(int32_t n, int32_t h, int32_t w, int32_t block);
+int rdeic_nr_moments(const uint8_t* rgb, int32_t n, int32_t h, int32_t w, int32_t block, float* ws, size_t ws_floats,
+                     double* out_scale0, double* out_scale1, void* stream);
+
 /* ------------------------------------------------------------ LPIPS (lpips.hip)
  * The kernels around the fp32 backbone convs of the LPIPS metric (reference model/lpips.py; network table and
  * weights: rdeic_amd/lpips.py). All activations fp32 NHWC with a pixel stride; every offset is 64-bit.

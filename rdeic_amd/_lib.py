@@ -133,6 +133,8 @@ PROTOTYPES = {
     "rdeic_rans_encode_batch": (C.c_int, [_i32, _p, _p, _sz, _sz, _p, _i32, _p, _p, _i32, _p, _sz, _p, _i32]),
     "rdeic_image_ssim_ws_floats": (C.c_size_t, [_i32, _i32, _i32, _i32]),
     "rdeic_image_ssim": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, C.c_size_t, _p, _p]),
+    "rdeic_nr_moments_ws_floats": (C.c_size_t, [_i32, _i32, _i32, _i32]),
+    "rdeic_nr_moments": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, C.c_size_t, _p, _p, _p]),
     # LPIPS (lpips.hip)
     "rdeic_lpips_prep": (C.c_int, [_p, _i32, _i32, _i32, _p, _p]),
     "rdeic_maxpool2d": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p]),
