@@ -411,6 +411,33 @@ int rdeic_conv_dgrad_small(const float* dz, int32_t ld_dz, const float* z, int32
                            int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride,
                            int32_t pad, int32_t prep_bwd, void* dx, int32_t ld_dx, int32_t dx_dtype, void* stream);
 
+/* ------------------------------------------------------------ DISTS (dists.hip)
+ * The kernels around the fp32 VGG16 backbone convs of the DISTS metric (Ding et al. 2020; network table, weights
+ * and chunking: rdeic_amd/dists.py). All activations fp32 NHWC with a pixel stride; every offset is 64-bit; no
+ * kernel uses an atomic.
+ * prep: uint8 RGB [n][h][w][3] -> raw and norm, both fp32 [n][h][w][4] (16-byte aligned): raw channels 0..2 are
+ * v / 255, norm's are (v / 255 - mean_c) / std_c in that order in fp32 (the ImageNet mean / std); channel 3 of
+ * both is zero. */
+int rdeic_dists_prep(const uint8_t* img, int32_t n, int32_t h, int32_t w, float* raw, float* norm, void* stream);
+/* L2 pool: out [n][ceil(h/2)][ceil(w/2)][c] = sqrt(sum_ij g_ij in(2 oy - 1 + i, 2 ox - 1 + j)^2 + 1e-12),
+ * g = [[1,2,1],[2,4,2],[1,2,1]] / 16, zero padding by bounds. */
+int rdeic_dists_l2pool(const float* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ld_in, float* out,
+                       int32_t ld_out, void* stream);
+/* Per image and channel of two maps x, y [n][hw][c]: out fp64 [n][5][c] = mx, my, vx, vy, cxy (biased, over the
+ * hw pixels). Two passes: the means, then the second moments about the means' fp32 roundings with the shift
+ * removed in fp64, so a large mean over a small spread does not cancel; vx, vy and cxy share one code path (two
+ * identical maps give the same bits in all three). A thread adds 8 fp32 terms at a time; everything else is fp64
+ * in a fixed order. An image's partial grid depends on (hw, c) only: its moments are the same in any batch and
+ * repeat bit for bit. ws: rdeic_dists_moments_ws_doubles(n, hw, c) doubles. */
+size_t rdeic_dists_moments_ws_doubles(int32_t n, int64_t hw, int32_t c);
+int rdeic_dists_moments(const float* x, int32_t ldx, const float* y, int32_t ldy, int32_t n, int64_t hw, int32_t c,
+                        double* ws, size_t ws_doubles, double* out, void* stream);
+/* out[img] (+= when accumulate) sum_c alpha_c S1_c + beta_c S2_c of the moments [n][5][c] of one tap, fp64 in a
+ * fixed order: S1 = (2 mx my + 1e-6) / (mx^2 + my^2 + 1e-6), S2 = (2 cxy + 1e-6) / (vx + vy + 1e-6).
+ * alpha, beta: c device doubles, already normalised by the sum over all taps. */
+int rdeic_dists_score(const double* mom, const double* alpha, const double* beta, int32_t n, int32_t c,
+                      int32_t accumulate, double* out, void* stream);
+
 /* ------------------------------------------------------------ host coders
  * Gaussian-conditional tables (compressai 1.2.4 GaussianConditional.update, precision 16).
  * pmf: [levels][pmf_ld] float32 pmf rows of length pmf_len[i] followed by the tail mass

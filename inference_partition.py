@@ -5,6 +5,7 @@
         [--steps 2] [--sampler ddpm|ddim] [--bf16 | --fp16] [--enable_resize_guard --max_long_side 1024
         --upsample_to_original] [--save_intermediates] [--max_images N]
         [--lpips_backbone PATH [--lpips_lin PATH] [--lpips_net alex|vgg]]
+        [--dists_weights PATH [--dists_backbone PATH]]
         [--captions_file FILE.json --clip_vocab bpe_simple_vocab_16e6.txt.gz]
 
 What it keeps from the reference:
@@ -37,6 +38,9 @@ What differs, all forced by the offline image or by design:
     --lpips_backbone names a torchvision AlexNet / VGG16 state dict (or the lpips package's full one);
     the `lin` heads come from --lpips_lin (default ./weight/lpips/<net>.pth, the reference's location).
     No backbone weights ship with the project: without --lpips_backbone the column is NaN;
+  * --dists_weights PATH (alpha / beta; the VGG16 convs from --dists_backbone or from the same file) adds DISTS
+    (rdeic_amd/dists.py) as a `dists` column after lpips, in the per-image line and in the averages; without the
+    flag the table and the prints are what they were;
   * noise comes from a CPU generator seeded per image (--seed + the image's index in sorted
     order), so results do not depend on how images are grouped into batches and micro-batches.
 """
@@ -157,9 +161,10 @@ def _save_intermediates(model, prefix: str, c_lat: torch.Tensor, hint: torch.Ten
     Image.fromarray(dec[0]).save(f"{prefix}_compressed.png")
 
 
-def compute_metrics(pred: np.ndarray, target: np.ndarray, lpips_model=None) -> Dict[str, float]:
+def compute_metrics(pred: np.ndarray, target: np.ndarray, lpips_model=None, dists_model=None) -> Dict[str, float]:
     """reference inference_partition.py:28-70 (pyiqa psnr / ssim / ms_ssim / lpips), on the device.
-    lpips_model: an rdeic_amd.lpips.LPIPS, or None (the column stays NaN)."""
+    lpips_model: an rdeic_amd.lpips.LPIPS, or None (the column stays NaN). dists_model: an rdeic_amd.dists.DISTS;
+    the `dists` key is there only with it."""
     from rdeic_amd import metrics
     from rdeic_amd.lpips import MIN_SIZE
     p = torch.from_numpy(np.ascontiguousarray(pred[None])).cuda()
@@ -173,7 +178,15 @@ def compute_metrics(pred: np.ndarray, target: np.ndarray, lpips_model=None) -> D
         out.update(ssim=float(metrics.ssim_levels(p, t, 1)[0, 0, 0]))
     if lpips_model is not None and min(pred.shape[:2]) >= MIN_SIZE[lpips_model.net]:
         out.update(lpips=float(metrics.lpips(p, t, lpips_model)[0]))
+    if dists_model is not None:
+        out.update(dists=float(metrics.dists(p, t, dists_model)[0]))
     return out
+
+
+def metrics_fieldnames(with_dists: bool = False, with_caption: bool = False) -> List[str]:
+    """The columns of metrics.csv: the reference's, `dists` after `lpips` with --dists_weights, `caption` last."""
+    return ["image", "bpp", "scale", "psnr", "ssim", "ms_ssim", "lpips"] + (["dists"] if with_dists else []) + \
+        (["caption"] if with_caption else [])
 
 
 def parse_args(argv=None) -> Namespace:
@@ -209,6 +222,11 @@ def parse_args(argv=None) -> Namespace:
     p.add_argument("--lpips_lin", type=str, default="",
                    help="the LPIPS lin heads (.pth as the reference's, or .npz); default ./weight/lpips/<net>.pth")
     p.add_argument("--lpips_net", type=str, default="alex", choices=["alex", "vgg"])
+    p.add_argument("--dists_weights", type=str, default="",
+                   help="DISTS alpha / beta (.pt / .pth / .npz); adds a dists column after lpips. Empty = no column")
+    p.add_argument("--dists_backbone", type=str, default="",
+                   help="torchvision VGG16 state dict (or the lpips package's) for DISTS; empty = the convs are "
+                        "read from --dists_weights (stage<k>.<i>.*)")
     p.add_argument("--captions_file", type=str, default="",
                    help="JSON {image path relative to --input: caption}: per-image text conditioning with "
                         "classifier-free guidance against the \"\" embedding (needs the text tower and --clip_vocab)")
@@ -230,6 +248,11 @@ def parse_args(argv=None) -> Namespace:
         for what, path in (("--lpips_backbone", args.lpips_backbone), ("--lpips_lin", args.lpips_lin)):
             if not os.path.isfile(path):
                 p.error(f"{what} {path} is not a file")
+    if args.dists_backbone and not args.dists_weights:
+        p.error("--dists_backbone needs --dists_weights")
+    for what, path in (("--dists_weights", args.dists_weights), ("--dists_backbone", args.dists_backbone)):
+        if path and not os.path.isfile(path):  # refused at start-up, before the model loads
+            p.error(f"{what} {path} is not a file")
     if args.fp16:
         print("[inference_partition] --fp16: the reduced-precision path computes in bf16 on MI355X "
               "(float16 autocast is not provided); same as --bf16", file=sys.stderr)
@@ -267,6 +290,10 @@ def main(argv=None) -> List[Dict]:
     if args.lpips_backbone:
         from rdeic_amd.lpips import LPIPS
         lpips_model = LPIPS(args.lpips_net, backbone=args.lpips_backbone, lin=args.lpips_lin)
+    dists_model = None
+    if args.dists_weights:
+        from rdeic_amd.dists import DISTS
+        dists_model = DISTS(args.dists_weights, backbone=args.dists_backbone or None)
     model = _load(args)
     captions: Optional[Dict[str, str]] = None
     if args.captions_file:
@@ -338,23 +365,23 @@ def main(argv=None) -> List[Dict]:
                 if up:
                     out = out.resize((m["orig_w"], m["orig_h"]), resample)
                 out.save(f"{prefix}.png")
-                vals = compute_metrics(np.array(out), orig if up else scaled, lpips_model)
+                vals = compute_metrics(np.array(out), orig if up else scaled, lpips_model, dists_model)
                 records.append({"image": rel, "bpp": bpp, "scale": m["scale"], **vals})
                 if texts is not None:
                     records[-1]["caption"] = texts[k]
                 bpps.append(bpp)
                 print(f"save to {prefix}.png, bpp {bpp:.3f}, PSNR {vals['psnr']:.2f}dB, SSIM {vals['ssim']:.4f}, "
-                      f"LPIPS {vals['lpips']:.4f}, time {per_image:.2f}s")
+                      f"LPIPS {vals['lpips']:.4f}, " +
+                      (f"DISTS {vals['dists']:.4f}, " if dists_model is not None else "") + f"time {per_image:.2f}s")
     if bpps:
         print(f"avg bpp: {sum(bpps) / len(bpps)}")
     if records:
         path = os.path.join(args.output, "metrics.csv")
         with open(path, "w", newline="") as fh:
-            w = csv.DictWriter(fh, fieldnames=["image", "bpp", "scale", "psnr", "ssim", "ms_ssim", "lpips"] +
-                               (["caption"] if captions is not None else []))
+            w = csv.DictWriter(fh, fieldnames=metrics_fieldnames(dists_model is not None, captions is not None))
             w.writeheader()
             w.writerows(records)
-        for k in ("psnr", "ssim", "ms_ssim", "lpips"):
+        for k in ("psnr", "ssim", "ms_ssim", "lpips") + (("dists",) if dists_model is not None else ()):
             v = np.array([r[k] for r in records], dtype=np.float64)
             print(f"Mean {k.upper()}: {np.nanmean(v) if np.isfinite(v).any() else float('nan'):.4f}")
         print(f"Metrics saved to {path}")

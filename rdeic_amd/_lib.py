@@ -145,6 +145,12 @@ PROTOTYPES = {
     "rdeic_maxpool2d_bwd": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p, _i32, _p]),
     "rdeic_conv_dgrad_small": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                          _i32, _i32, _p, _i32, _i32, _p]),
+    # DISTS (dists.hip)
+    "rdeic_dists_prep": (C.c_int, [_p, _i32, _i32, _i32, _p, _p, _p]),
+    "rdeic_dists_l2pool": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p]),
+    "rdeic_dists_moments_ws_doubles": (_sz, [_i32, _i64, _i32]),
+    "rdeic_dists_moments": (C.c_int, [_p, _i32, _p, _i32, _i32, _i64, _i32, _p, _sz, _p, _p]),
+    "rdeic_dists_score": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p]),
     "rdeic_groupnorm_parts_floats": (C.c_size_t, [_i64, _i32, _i32]),
     "rdeic_groupnorm_parts_ab": (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _i32, _f, _p, _p, _p, _p]),
     "rdeic_groupnorm_parts_apply": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _f, _p, _p,

@@ -1,0 +1,259 @@
+"""DISTS (Ding, Ma, Wang, Simoncelli 2020) on the device, the metric forward only.
+
+The network is the VGG16 feature stack LPIPS("vgg") runs (the library's fp32 convs, ReLU in the epilogue), with
+an L2 Hanning pool where VGG has its max pools, the input image itself as a sixth (first) tap, and per tap and
+channel two SSIM-like ratios of the global means, variances and covariance, weighted by the learned `alpha` and
+`beta` (1475 values each). Four kernels of dists.hip sit around the convs: the prep (uint8 -> the raw v / 255
+tap and the ImageNet-normalised conv input, both fp32 NHWC with a zero fourth channel), the L2 pool, the
+two-pass channel moments in fp64 and the per-tap score.
+
+No weights ship with the project: the caller passes `alpha` / `beta` (.pt / .pth / .npz, or a dict) and the
+torchvision VGG16 state dict (``features.<i>.*``), the lpips package's, or a weights file that carries the convs
+itself as ``stage<k>.<i>.*``. The computation is pinned against an fp64 restatement of the published algorithm
+with a seeded backbone and seeded weights (tests/dists_ref.py); parity with pyiqa, DISTS_pytorch, the published
+alpha / beta and torchvision's weights is unpinned, none of them is available offline.
+
+Scores are batch-invariant bit for bit: split-K is pinned off for the backbone convs, every conv output element
+is one fixed-order k sum, the pool is element-wise, and the moment kernels' partial grid depends on the tap shape
+only. The batch is therefore chunked freely (chunk_pairs) to keep every activation tensor under 2^31 bytes.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, List, Optional, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib, lpips as _lpips, ops
+
+CHANNELS = (3, 64, 128, 256, 512, 512)  # per tap; the image itself first
+N_WEIGHTS = sum(CHANNELS)  # 1475
+MAX_TENSOR_BYTES = 2 ** 31
+MAX_PAIRS = 32768  # per launch: rdeic_dists_moments takes at most 65535 images
+_TABLE = _lpips.NETS["vgg"]  # ("conv", ...) / ("pool", 2, 2) / ("tap",): the pools become L2 pools here
+
+
+def activation_shapes(h: int, w: int) -> List[Tuple[int, int, int]]:
+    """(h, w, c) of every activation tensor of one image: the two 4-channel prep outputs (raw, normalised), then
+    every conv and L2-pool output in forward order. The pools halve with ceil: (h + 2 - 3) // 2 + 1."""
+    if h < 1 or w < 1:
+        raise ValueError(f"DISTS needs a non-empty image, got {h}x{w}")
+    shapes, c = [(h, w, 4), (h, w, 4)], 4
+    for op in _TABLE:
+        if op[0] == "conv":
+            c = op[2]  # 3x3, stride 1, pad 1: the size stays
+        elif op[0] == "pool":
+            h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+        else:
+            continue
+        shapes.append((h, w, c))
+    return shapes
+
+
+def tap_shapes(h: int, w: int) -> List[Tuple[int, int, int]]:
+    """(h, w, c) of the six taps; tap 0 is the 4-channel raw image (3 channels used)."""
+    acts, taps, i = activation_shapes(h, w), [], 1
+    taps.append(acts[0])
+    for op in _TABLE:
+        if op[0] == "tap":
+            taps.append(acts[i])
+        else:
+            i += 1
+    return taps
+
+
+def image_bytes(h: int, w: int) -> int:
+    """fp32 bytes of the largest activation tensor of one image."""
+    return max(4 * a * b * c for a, b, c in activation_shapes(h, w))
+
+
+def chunk_pairs(h: int, w: int) -> int:
+    """Image pairs per backbone launch, a function of (H, W) alone: the most for which every activation of the
+    2 x pairs images stays under 2^31 bytes, at least 1 (then split_pair may still apply) and at most MAX_PAIRS
+    (the moment kernels take the image from the grid's third dimension). An image whose own activations reach
+    2^31 bytes is refused."""
+    per = image_bytes(h, w)
+    if per >= MAX_TENSOR_BYTES:
+        raise ValueError(f"DISTS at {h}x{w}: one image's activation reaches 2^31 bytes")
+    return min(MAX_PAIRS, max(1, ((MAX_TENSOR_BYTES - 1) // per) // 2))
+
+
+def split_pair(h: int, w: int) -> bool:
+    """True where even one pair's activations would reach 2^31 bytes in one launch."""
+    return 2 * image_bytes(h, w) >= MAX_TENSOR_BYTES
+
+
+def _load_file(path: str) -> Dict[str, torch.Tensor]:
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"DISTS weights not found: {path}")
+    if str(path).endswith(".npz"):
+        with np.load(path) as z:
+            return {k: torch.from_numpy(np.array(z[k])) for k in z.files}
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    return sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+
+
+def load_weights(src: Union[str, Dict]) -> Tuple[np.ndarray, np.ndarray]:
+    """(alpha, beta) as float64 [1475] from a path (.pt / .pth / .npz) or a dict holding `alpha` and `beta`,
+    [1, 1475, 1, 1] or flat."""
+    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    out = []
+    for name in ("alpha", "beta"):
+        if name not in sd:
+            raise ValueError(f"DISTS weights: no '{name}' found; got {sorted(sd)[:6]}{' ...' if len(sd) > 6 else ''}")
+        v = torch.as_tensor(sd[name]).detach().to("cpu", torch.float64).reshape(-1).numpy().copy()
+        if v.size != N_WEIGHTS:
+            raise ValueError(f"DISTS {name}: {v.size} weights, expected {N_WEIGHTS} (sum of {CHANNELS})")
+        out.append(v)
+    return out[0], out[1]
+
+
+def load_backbone(src: Union[str, Dict[str, torch.Tensor]]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """[(weight [cout,cin,3,3], bias [cout])] fp32 CPU tensors of the 13 convs, in order, from the torchvision
+    VGG16 state dict (features.<i>.*), the lpips package's (net.slice<k>.<i>.*), or the single-file layout
+    stage<k>.<i>.* (<i> the torchvision features index)."""
+    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    layers = _lpips.conv_layers("vgg")
+    stage = [f"stage{k}.{i}" for i, k, *_ in layers]
+    if all(f"{n}.weight" in sd and f"{n}.bias" in sd for n in stage):
+        sd = {f"features.{i}.{p}": sd[f"{n}.{p}"] for n, (i, *_) in zip(stage, layers) for p in ("weight", "bias")}
+    try:
+        return _lpips.load_backbone("vgg", sd)
+    except ValueError as e:
+        if "expected the torchvision keys" not in str(e):
+            raise  # a shape error: it names its tensor
+        raise ValueError(f"DISTS backbone: expected the torchvision keys features.0.weight/.bias ... "
+                         f"features.28.weight/.bias, the lpips package's net.slice1.0.weight/.bias ... "
+                         f"net.slice5.28.weight/.bias, or {stage[0]}.weight/.bias ... {stage[-1]}.weight/.bias; "
+                         f"got {sorted(sd)[:6]}{' ...' if len(sd) > 6 else ''}") from None
+
+
+def seeded_weights(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Stand-in alpha / beta [1, 1475, 1, 1] from N(0.1, 0.01), the published implementation's initialisation, for
+    tests and benchmarks (no trained weights ship)."""
+    g = torch.Generator().manual_seed(seed)
+    return {"alpha": 0.1 + 0.01 * torch.randn((1, N_WEIGHTS, 1, 1), generator=g),
+            "beta": 0.1 + 0.01 * torch.randn((1, N_WEIGHTS, 1, 1), generator=g)}
+
+
+def prep(img_u8: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """uint8 [n, h, w, 3] -> (raw, normalised), both fp32 [n, h, w, 4] with a zero fourth channel."""
+    n, h, w, _ = img_u8.shape
+    raw = torch.empty((n, h, w, 4), dtype=torch.float32, device=img_u8.device)
+    norm = torch.empty((n, h, w, 4), dtype=torch.float32, device=img_u8.device)
+    ops.call("rdeic_dists_prep", img_u8.contiguous().data_ptr(), n, h, w, raw.data_ptr(), norm.data_ptr(),
+             ops.stream_ptr())
+    return raw, norm
+
+
+def l2_pool(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sqrt(depthwise 3x3 Hanning conv of x^2, stride 2, zero padding 1, + 1e-12) of an fp32 NHWC activation."""
+    n, h, w, c = x.shape
+    if x.dtype != torch.float32 or min(n, h, w, c) < 1:
+        raise ValueError(f"l2_pool: non-empty fp32 [n, h, w, c] expected, got {tuple(x.shape)} {x.dtype}")
+    ho, wo = (h + 1) // 2, (w + 1) // 2
+    if out is None:
+        out = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, ho, wo, c) or out.dtype != torch.float32:
+        raise ValueError(f"l2_pool: out must be fp32 {(n, ho, wo, c)}")
+    ops.call("rdeic_dists_l2pool", x.data_ptr(), n, h, w, c, ops.pix_ld(x), out.data_ptr(), ops.pix_ld(out),
+             ops.stream_ptr())
+    return out
+
+
+def moments(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """fp64 [n, 5, c]: mx, my, vx, vy, cxy (biased) per image and channel of two fp32 NHWC maps of one shape."""
+    if x.shape != y.shape or x.dim() != 4 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError("moments: two non-empty fp32 [n, h, w, c] maps of one shape expected")
+    n, h, w, c = x.shape
+    nd = int(_lib.load().rdeic_dists_moments_ws_doubles(n, h * w, c))
+    ws = torch.empty(max(nd, 1), dtype=torch.float64, device=x.device)
+    out = torch.empty((n, 5, c), dtype=torch.float64, device=x.device)
+    ops.call("rdeic_dists_moments", x.data_ptr(), ops.pix_ld(x), y.data_ptr(), ops.pix_ld(y), n, h * w, c,
+             ws.data_ptr(), nd, out.data_ptr(), ops.stream_ptr())
+    return out
+
+
+def tap_score(mom: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, out: Optional[torch.Tensor] = None,
+              accumulate: bool = False) -> torch.Tensor:
+    """out[n] (+)= sum_c alpha_c S1_c + beta_c S2_c of the moments [n, 5, c] of one tap (fp64 throughout)."""
+    n, _, c = mom.shape
+    for v in (alpha, beta):
+        if v.dtype != torch.float64 or v.numel() != c or not v.is_contiguous():
+            raise ValueError(f"tap_score: alpha and beta must be {c} contiguous fp64 weights")
+    if mom.dtype != torch.float64 or mom.shape[1] != 5 or not mom.is_contiguous():
+        raise ValueError("tap_score: contiguous fp64 [n, 5, c] moments expected")
+    if out is None:
+        if accumulate:
+            raise ValueError("tap_score: accumulate needs out")
+        out = torch.empty(n, dtype=torch.float64, device=mom.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (n,) or not out.is_contiguous():
+        raise ValueError(f"tap_score: out must be contiguous fp64 [{n}]")
+    ops.call("rdeic_dists_score", mom.data_ptr(), alpha.data_ptr(), beta.data_ptr(), n, c, int(accumulate),
+             out.data_ptr(), ops.stream_ptr())
+    return out
+
+
+class DISTS:
+    """DISTS(weights, backbone)(pred_u8, target_u8): uint8 [N, H, W, 3] device tensors -> float64 numpy [N]."""
+
+    def __init__(self, weights=None, backbone=None, device="cuda"):
+        if weights is None:
+            raise ValueError("DISTS needs its alpha / beta weights and a VGG16 backbone; none ship with the project")
+        self.device = torch.device(device)
+        wsd = _load_file(weights) if isinstance(weights, (str, os.PathLike)) else weights
+        alpha, beta = load_weights(wsd)
+        raw = load_backbone(wsd if backbone is None else backbone)
+        layers = _lpips.conv_layers("vgg")
+        self.convs = []
+        for i, (wt, b) in enumerate(raw):
+            if i == 0:  # zero fourth input channel (the prep kernel's): exact zero products, 16-byte gathers
+                wt = torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, 1))
+            _, _, _, _, _, s, p = layers[i]
+            self.convs.append(ops.ConvParams.pack(wt, b, stride=s, pad=p, dtype=torch.float32))
+        # normalised once in fp64; per tap, padded with zeros to the tap's stored channel count (4 at tap 0)
+        total = alpha.sum() + beta.sum()
+        self.alpha, self.beta, c0 = [], [], 0
+        for c in CHANNELS:
+            pad = (-c) % 4
+            for dst, v in ((self.alpha, alpha), (self.beta, beta)):
+                dst.append(torch.from_numpy(np.concatenate([v[c0:c0 + c] / total, np.zeros(pad)])).to(self.device))
+            c0 += c
+
+    def features(self, img_u8: torch.Tensor) -> List[torch.Tensor]:
+        """The six taps [n, h_k, w_k, C_k] fp32 of uint8 [n, H, W, 3] images (tap 0: 4 channels, the last zero)."""
+        raw, x = prep(img_u8)
+        taps, ci = [raw], 0
+        with ops.splitk_as((False, False)):  # a k grouping that depended on the batch would break invariance
+            for op in _TABLE:
+                if op[0] == "conv":
+                    x = ops.conv2d(x, self.convs[ci], act=ops.LEAKY, slope=0.0)
+                    ci += 1
+                elif op[0] == "pool":
+                    x = l2_pool(x)
+                else:
+                    taps.append(x)
+        return taps
+
+    def _chunk(self, pred: torch.Tensor, tgt: torch.Tensor, out: torch.Tensor) -> None:
+        n, h, w, _ = pred.shape
+        if split_pair(h, w):
+            f0, f1 = self.features(pred), self.features(tgt)
+        else:
+            f = self.features(torch.cat([pred, tgt]))
+            f0, f1 = [t[:n] for t in f], [t[n:] for t in f]
+        for k, (a, b) in enumerate(zip(f0, f1)):
+            tap_score(moments(a, b), self.alpha[k], self.beta[k], out=out, accumulate=k > 0)
+
+    def __call__(self, pred_u8: torch.Tensor, target_u8: torch.Tensor, chunk: Optional[int] = None) -> np.ndarray:
+        """chunk: pairs per backbone launch (default chunk_pairs(H, W)); it never changes a score."""
+        if pred_u8.shape != target_u8.shape or pred_u8.dim() != 4 or pred_u8.shape[3] != 3 \
+                or pred_u8.dtype != torch.uint8 or target_u8.dtype != torch.uint8:
+            raise ValueError("expected matching uint8 [N, H, W, 3] images")
+        n, h, w, _ = pred_u8.shape
+        step = min(chunk_pairs(h, w), int(chunk) if chunk else n) if n else 1  # validates the size
+        out = torch.empty(n, dtype=torch.float64, device=pred_u8.device)
+        for s0 in range(0, n, max(1, step)):
+            self._chunk(pred_u8[s0:s0 + step], target_u8[s0:s0 + step], out[s0:s0 + step])
+        return 1.0 - out.cpu().numpy()

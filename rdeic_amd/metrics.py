@@ -57,6 +57,11 @@ def lpips(pred_u8: torch.Tensor, target_u8: torch.Tensor, model) -> np.ndarray:
     return model(pred_u8, target_u8)
 
 
+def dists(pred_u8: torch.Tensor, target_u8: torch.Tensor, model) -> np.ndarray:
+    """Per-image DISTS [N] (float64) of uint8 [N,H,W,3] device tensors; model: an rdeic_amd.dists.DISTS."""
+    return model(pred_u8, target_u8)
+
+
 # ------------------------------------------------------------------ no-reference metrics (NIQE, BRISQUE)
 # The reference's experiments/run_ood.py:93-127 scores reconstructions with pyiqa "niqe" / "brisque". pyiqa and its
 # model files are not in this image: the published algorithms (Mittal, Soundararajan, Bovik 2013; Mittal, Moorthy,

@@ -63,8 +63,18 @@ def select_candidate(scores: Optional[np.ndarray]) -> int:
     return 0 if scores is None else int(np.argmin(scores))
 
 
-def score_image(pred: torch.Tensor, target: torch.Tensor, lpips=None, niqe_model=None, brisque_model=None) -> Dict:
-    """The metric columns of one cropped reconstruction against its original: uint8 [1,H,W,3] device tensors."""
+def columns(with_dists: bool = False) -> List[str]:
+    """COLUMNS, with `dists` after `lpips` when a DISTS model scores the run."""
+    if not with_dists:
+        return list(COLUMNS)
+    i = COLUMNS.index("lpips") + 1
+    return COLUMNS[:i] + ["dists"] + COLUMNS[i:]
+
+
+def score_image(pred: torch.Tensor, target: torch.Tensor, lpips=None, niqe_model=None, brisque_model=None,
+                dists=None) -> Dict:
+    """The metric columns of one cropped reconstruction against its original: uint8 [1,H,W,3] device tensors.
+    dists: an rdeic_amd.dists.DISTS; the `dists` key is there only with it."""
     from .lpips import MIN_SIZE
     h, w = pred.shape[1:3]
     out = {"psnr": float(metrics.psnr(pred, target)[0]), "ssim": NAN, "ms_ssim": NAN, "lpips": NAN, "niqe": NAN,
@@ -77,6 +87,8 @@ def score_image(pred: torch.Tensor, target: torch.Tensor, lpips=None, niqe_model
         out.update(ssim=float(metrics.ssim_levels(pred, target, 1)[0, 0, 0]))
     if lpips is not None and min(h, w) >= MIN_SIZE[lpips.net]:
         out["lpips"] = float(lpips(pred, target)[0])
+    if dists is not None:
+        out["dists"] = float(dists(pred, target)[0])
     if niqe_model is not None:
         out["niqe"] = float(metrics.niqe(pred, niqe_model)[0])
     if brisque_model is not None and h % 2 == 0 and w % 2 == 0 and min(h, w) >= 8:
@@ -88,8 +100,9 @@ def score_image(pred: torch.Tensor, target: torch.Tensor, lpips=None, niqe_model
 def run_domain(model, files: Sequence[str], context: torch.Tensor, domain: str = "", cache_dir: str = "encodings/ood",
                sampler: str = "ddpm", steps: int = 2, guidance_scale: float = 1.0, latent_noise_std: float = 0.0,
                num_noise_samples: int = 1, seed: int = 231, batch_size: int = 1, lpips=None, niqe_model=None,
-               brisque_model=None, recon_dir: Optional[str] = None) -> List[Dict]:
-    """One domain's images through the codec; one record per image (COLUMNS), in sorted file order."""
+               brisque_model=None, recon_dir: Optional[str] = None, dists=None) -> List[Dict]:
+    """One domain's images through the codec; one record per image (COLUMNS, and `dists` with a DISTS model), in
+    sorted file order. The best-of-N candidate is chosen on LPIPS alone."""
     from PIL import Image
     del guidance_scale  # no unconditional branch in the reference's call: no effect there either
     files = sorted(files)
@@ -161,7 +174,7 @@ def run_domain(model, files: Sequence[str], context: torch.Tensor, domain: str =
                     rec = {"domain": domain, "image_id": stem,
                            "bpp": 8.0 * os.path.getsize(os.path.join(stream_dir, stem)) / (H * W)}
                     rec.update(score_image(pred, torch.from_numpy(orig[None]).to(dev), lpips, niqe_model,
-                                           brisque_model))
+                                           brisque_model, dists=dists))
                     if recon_dir:
                         Image.fromarray(pred[0].cpu().numpy()).save(os.path.join(recon_dir, f"{stem}.png"))
                     done[f] = rec
@@ -170,22 +183,23 @@ def run_domain(model, files: Sequence[str], context: torch.Tensor, domain: str =
     return [done[f] for f in files if f in done]
 
 
-def write_csv(records: Sequence[Dict], path: str) -> None:
-    """The reference's table (run_ood.py:356-362, :376-378): COLUMNS in order, NaN for what was not scored."""
+def write_csv(records: Sequence[Dict], path: str, with_dists: bool = False) -> None:
+    """The reference's table (run_ood.py:356-362, :376-378): COLUMNS in order, NaN for what was not scored;
+    with_dists adds the `dists` column after `lpips`."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=COLUMNS, restval=NAN, extrasaction="ignore")
+        w = csv.DictWriter(f, fieldnames=columns(with_dists), restval=NAN, extrasaction="ignore")
         w.writeheader()
         for r in records:
             w.writerow(r)
 
 
-def summary(records: Sequence[Dict]) -> Dict[str, Dict[str, Tuple[float, float]]]:
+def summary(records: Sequence[Dict], with_dists: bool = False) -> Dict[str, Dict[str, Tuple[float, float]]]:
     """{domain: {column: (mean, sample std)}} over each domain's finite values (run_ood.py:396-405)."""
     out: Dict[str, Dict[str, Tuple[float, float]]] = {}
     for d in sorted({r["domain"] for r in records}):
         out[d] = {}
-        for k in COLUMNS[2:]:
+        for k in columns(with_dists)[2:]:
             v = np.array([r.get(k, NAN) for r in records if r["domain"] == d], dtype=np.float64)
             v = v[np.isfinite(v)]
             out[d][k] = (float(v.mean()) if v.size else NAN, float(v.std(ddof=1)) if v.size > 1 else NAN)

@@ -4,6 +4,7 @@
         [--latent_noise_std S --num_noise_samples N] [--output_dir indicators/] [--cache_dir encodings/ood/]
         [--save_recon] [--seed 231] [--ckpt FILE] [--dtype fp32|bf16] [--batch_size 1]
         [--lpips_backbone PATH [--lpips_lin PATH]] [--niqe_model FILE] [--brisque_model FILE]
+        [--dists_weights PATH [--dists_backbone PATH]]
 
 Per domain folder: pad to x64 -> compress to `<cache_dir>/<domain>/<stem>` -> decompress from that file -> relay
 decode -> crop -> score against the original (rdeic_amd/ood.py). Writes `<output_dir>/ood_results_<domain>.csv` per
@@ -15,6 +16,9 @@ Differences from the reference, all forced by the offline image or by design:
     --lpips_backbone (AlexNet, as pyiqa "lpips"), niqe without --niqe_model (the published niqe_modelparameters.mat, or
     .npz / .safetensors with mu_prisparam, cov_prisparam) and brisque without --brisque_model (.npz / .safetensors
     with sv, sv_coef, rho, gamma, scale_min, scale_max);
+  * --dists_weights PATH (alpha / beta; the VGG16 convs from --dists_backbone or from the same file) adds DISTS
+    (rdeic_amd/dists.py) as a `dists` column after lpips; without the flag the tables are what they were. The
+    best-of-N candidate is still chosen on LPIPS;
   * noise comes from a CPU generator seeded per image (--seed + the image's index in its domain's sorted order), so
     results do not depend on --batch_size.
 """
@@ -59,10 +63,18 @@ def parse_args(argv=None) -> Namespace:
     p.add_argument("--brisque_model", type=str, default="",
                    help=".npz / .safetensors with sv, sv_coef, rho, gamma, scale_min, scale_max; "
                         "empty = brisque column NaN")
+    p.add_argument("--dists_weights", type=str, default="",
+                   help="DISTS alpha / beta (.pt / .pth / .npz); adds a dists column after lpips. Empty = no column")
+    p.add_argument("--dists_backbone", type=str, default="",
+                   help="torchvision VGG16 state dict (or the lpips package's) for DISTS; empty = the convs are "
+                        "read from --dists_weights (stage<k>.<i>.*)")
     args = p.parse_args(argv)
     if args.lpips_backbone and not args.lpips_lin:
         args.lpips_lin = os.path.join(".", "weight", "lpips", "alex.pth")
-    for what in ("lpips_backbone", "lpips_lin", "niqe_model", "brisque_model"):  # refused at start-up
+    if args.dists_backbone and not args.dists_weights:
+        p.error("--dists_backbone needs --dists_weights")
+    for what in ("lpips_backbone", "lpips_lin", "niqe_model", "brisque_model", "dists_weights",
+                 "dists_backbone"):  # refused at start-up
         path = getattr(args, what)
         if path and not os.path.isfile(path):
             p.error(f"--{what} {path} is not a file")
@@ -71,11 +83,11 @@ def parse_args(argv=None) -> Namespace:
     return args
 
 
-def print_summary(records: List[Dict]) -> None:
-    from rdeic_amd.ood import COLUMNS, summary
+def print_summary(records: List[Dict], with_dists: bool = False) -> None:
+    from rdeic_amd.ood import columns, summary
     print("\n=== Overall Summary by Domain (mean, std) ===")
-    for domain, cols in summary(records).items():
-        print(f"{domain}: " + ", ".join(f"{k} {cols[k][0]:.4f} ({cols[k][1]:.4f})" for k in COLUMNS[2:]))
+    for domain, cols in summary(records, with_dists).items():
+        print(f"{domain}: " + ", ".join(f"{k} {cols[k][0]:.4f} ({cols[k][1]:.4f})" for k in columns(with_dists)[2:]))
 
 
 def main(argv=None) -> List[Dict]:
@@ -90,6 +102,10 @@ def main(argv=None) -> List[Dict]:
     if args.lpips_backbone:
         from rdeic_amd.lpips import LPIPS
         lpips_model = LPIPS("alex", backbone=args.lpips_backbone, lin=args.lpips_lin)
+    dists_model = None
+    if args.dists_weights:
+        from rdeic_amd.dists import DISTS
+        dists_model = DISTS(args.dists_weights, backbone=args.dists_backbone or None)
     niqe_model = metrics.NIQE(args.niqe_model) if args.niqe_model else None
     brisque_model = metrics.BRISQUE(args.brisque_model) if args.brisque_model else None
     model = load_model(args.ckpt, args.dtype)
@@ -112,17 +128,17 @@ def main(argv=None) -> List[Dict]:
             guidance_scale=args.guidance_scale, latent_noise_std=args.latent_noise_std,
             num_noise_samples=args.num_noise_samples, seed=args.seed, batch_size=args.batch_size, lpips=lpips_model,
             niqe_model=niqe_model, brisque_model=brisque_model,
-            recon_dir=os.path.join(args.output_dir, name) if args.save_recon else None)
+            recon_dir=os.path.join(args.output_dir, name) if args.save_recon else None, dists=dists_model)
         if records:
             path = os.path.join(args.output_dir, f"ood_results_{name}.csv")
-            ood.write_csv(records, path)
+            ood.write_csv(records, path, dists_model is not None)
             print(f"Domain results saved to {path}")
             all_records += records
     if all_records:
         path = os.path.join(args.output_dir, "ood_results_all.csv")
-        ood.write_csv(all_records, path)
+        ood.write_csv(all_records, path, dists_model is not None)
         print(f"\nConsolidated results saved to {path}")
-        print_summary(all_records)
+        print_summary(all_records, dists_model is not None)
     return all_records
 
 
