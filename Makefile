@@ -14,11 +14,11 @@ CXXFLAGS := -O3 -fPIC -std=c++17 -Wall -pthread
 
 all: $(LIB) oracle
 
-$(BUILD)/%.hip.o: rdeic_amd/csrc/%.hip rdeic_amd/csrc/common.h rdeic_amd/csrc/conv_common.h rdeic_amd/csrc/prof.h include/rdeic_hip.h
+$(BUILD)/%.hip.o: rdeic_amd/csrc/%.hip rdeic_amd/csrc/common.h rdeic_amd/csrc/conv_common.h rdeic_amd/csrc/conv_route.h rdeic_amd/csrc/prof.h include/rdeic_hip.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/%.cpp.o: rdeic_amd/csrc/%.cpp include/rdeic_hip.h
+$(BUILD)/%.cpp.o: rdeic_amd/csrc/%.cpp rdeic_amd/csrc/conv_route.h include/rdeic_hip.h
 	@mkdir -p $(BUILD)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 

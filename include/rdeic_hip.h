@@ -87,16 +87,36 @@ typedef struct rdeic_conv_desc {
   const float* ln_colsum;
 } rdeic_conv_desc;
 
+/* Dispatch: plan, then launch. A conv is planned by host arithmetic alone (rdeic_conv2d_plan, conv_route.cpp)
+ * before anything is launched: the descriptor is validated, ONE route is chosen, and a launch whose activation
+ * spans pass the launch limit is cut into slices (image groups, or row bands of each image), every one of which
+ * is checked. The routes, in the order they are tried:
+ *   EDGE_IN8     conv_in of the VAE: 3x3 from 8 channels to <= 128, bias only, w % 64 == 0 (option 10)
+ *   EDGE_NARROW  GroupNorm (+ SiLU) -> 3x3 conv to <= 16 channels, h % 8 == 0, w % 64 == 0 (option 10)
+ *   DMA          out_mode 2 (fused GEGLU) always, whatever option 5 says; -22 where the LDS-DMA kernel cannot take it
+ *   HALO         3x3 / stride 1 / pad 1 on 4 x 64 or 8 x 64 pixel tiles x 128 channels, c0 % 32 == 0, c0 <= 512:
+ *                GroupNorm inputs up to 512 output channels (option 6 = 1), every eligible conv (option 6 = 2)
+ *   MATERIALIZE  (rdeic_conv2d_plan only) the descriptor has gn_ab, no fused-GroupNorm kernel above takes it, and
+ *                without gn_ab it would run on DMA / TILE, or it has cout <= 4 and at least 2^20 pixels: the caller
+ *                should apply the GroupNorm first (rdeic_groupnorm_apply / _parts_apply) and call again without
+ *                gn_ab. rdeic_conv2d itself runs such a descriptor on the routes below (the gather's prologue).
+ *   SMALLC       bf16 3x3 / stride 1 / pad 1 to <= 4 channels, c0 % 32 == 0 (VALU dot2 kernel)
+ *   DMA          bf16, 16-byte gathers, cout > 32, no gn_ab, both concat segments multiples of 64 channels
+ *                (option 5; rdeic_conv2d only, or an explicit tile >= 20)
+ *   TILE         the same without the 64-channel alignment: register-staged big tiles
+ *   DIRECT       everything else (fp32, cout <= 32, unaligned inputs, gn_ab prologue, conv path 0)
+ * rdeic_conv2d plans with tile -2 ("no tile given"). */
 int rdeic_conv2d(const rdeic_conv_desc* d, void* stream);
-/* rdeic_conv2d with an explicit tile. Register-staged tiles (any bf16 conv without a GN
- * prologue): 0 256x256/16 waves, 1 256x128/8, 2 128x256/8, 3 128x128/4, 4 64x128/4,
- * 6 256x128/16, 7 128x256/16, 8 128x128/8, 9 128x128/16, 10 64x128/8. LDS-DMA tiles (bf16, both
- * concat segments multiples of 64 channels; other shapes fall back to the register path):
+/* rdeic_conv2d with an explicit tile, for routes DMA and TILE (every other route ignores it). Register-staged
+ * tiles: 0 256x256/16 waves, 1 256x128/8, 2 128x256/8, 3 128x128/4, 4 64x128/4,
+ * 6 256x128/16, 7 128x256/16, 8 128x128/8, 9 128x128/16, 10 64x128/8. LDS-DMA tiles:
  * 21 256x128/8, 22 128x256/8, 23-24 128x128/4, 25 128x128/8, 26 64x128/4,
  * 27 128x128/8, 28 256x128/8, 29 128x256/8, 30 64x128/4, 31 128x64/4, 32 256x256/16,
  * 33 256x128/16, 34 128x128/16, 35 512x128/16, 36 64x128/8, 37 128x160/4, 38 64x160/4
  * (ring depths in conv_dma.hip). -1 = heuristic.
- * All tiles give
+ * The tile also picks between the two routes: a tile >= 20 takes DMA where the shape allows it (even with
+ * option 5 at 0) and TILE's heuristic where not; a tile in -1 .. 19 takes TILE. With an explicit tile a conv
+ * without gn_ab stays on these two routes under option 6 = 2 as well. All tiles give
  * bit-identical results (same k order, same MFMA), so a caller may autotune. */
 int rdeic_conv2d_tile(const rdeic_conv_desc* d, int32_t tile, void* stream);
 /* Split-K variant for small-M / large-K layers (the UNet's 8x8 and 16x16 levels): `splits`
@@ -121,17 +141,35 @@ int rdeic_conv2d_splitk(const rdeic_conv_desc* d, int32_t splits, float* ws, siz
  * rdeic_conv2d with the 3x3 weights), or a negative error. */
 int rdeic_conv2d_up2_phases(const rdeic_conv_desc* d, int64_t phase_stride, int32_t tile, void* stream);
 int rdeic_conv2d_up2_group(const rdeic_conv_desc* d);
-/* Row bands (host arithmetic only). The LDS-DMA, halo, phase and narrow kernels address activations through
+/* Slices (host arithmetic only). The LDS-DMA, halo, phase and narrow kernels address activations through
  * 32-bit byte offsets. A launch over several images past the launch limit (rdeic_set_conv_option key 12) runs as
- * groups of whole images; ONE image past it runs as bands of output rows, each a launch of the same kernel on a
- * row window of the input and of the output (out_mode 0, batch 1, bf16). Outputs and fused statistics are
- * bit-identical to one launch, for any limit.
- * Returns the output rows per band of d's image under the current limit: d->ho when the image fits, 0 when not
- * even one row tile fits (the conv then takes its slower general kernel), else a multiple of row_tile (4 / 8:
+ * groups of whole images (the largest group that fits; the phase path evens the groups out); ONE image past it
+ * runs as bands of output rows, each a launch of the same kernel on a row window of the input and of the output
+ * (out_mode 0, batch 1, bf16). Outputs and fused statistics are bit-identical to one launch, for any limit.
+ * rdeic_conv2d_band_rows returns the output rows per band of d's image under the current limit: d->ho when the
+ * image fits, 0 when not even one row tile fits (the route is then not taken), else a multiple of row_tile (4 / 8:
  * the halo kernels, 8: the narrow kernel, <= 1: the LDS-DMA tiles; 2 at least for up2) and, when d->gn_part is
  * set, of whole 64-row statistic blocks (rows * wo % 64 == 0; up2: % 256, a block per phase). Every band's
  * input, output and residual spans are <= the limit; the last band may be shorter. */
 int rdeic_conv2d_band_rows(const rdeic_conv_desc* d, int32_t row_tile);
+/* The plan of rdeic_conv2d (tile -2) / rdeic_conv2d_tile (tile >= -1) for d under the current switches: host
+ * arithmetic only, nothing is read through d's pointers. Returns what the call would return before launching
+ * anything: 0, or -22. images x rows: what one launch covers; launches: how many slices the conv runs as. */
+#define RDEIC_ROUTE_EDGE_IN8 0
+#define RDEIC_ROUTE_EDGE_NARROW 1
+#define RDEIC_ROUTE_HALO 2
+#define RDEIC_ROUTE_SMALLC 3
+#define RDEIC_ROUTE_DMA 4
+#define RDEIC_ROUTE_TILE 5
+#define RDEIC_ROUTE_DIRECT 6
+#define RDEIC_ROUTE_MATERIALIZE 7
+typedef struct rdeic_conv_plan {
+  int32_t route;    /* RDEIC_ROUTE_* */
+  int32_t images;   /* images per launch */
+  int32_t rows;     /* output rows per launch */
+  int32_t launches;
+} rdeic_conv_plan;
+int rdeic_conv2d_plan(const rdeic_conv_desc* d, int32_t tile, rdeic_conv_plan* plan);
 /* 2 (default): bf16 convs without a GN prologue pick among the big register-staged tiles
  * (256x256 / 256x128 / 128x256 / 128x128 / 64x128 / 128x64); 0: the 128-tile kernel with the
  * fused GroupNorm prologue everywhere (A/B timing, debugging). Results are bit-identical.

@@ -51,6 +51,16 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvPlan(C.Structure):
+    """Mirror of rdeic_conv_plan (rdeic_conv2d_plan)."""
+    _fields_ = [("route", C.c_int32), ("images", C.c_int32), ("rows", C.c_int32), ("launches", C.c_int32)]
+
+
+# RDEIC_ROUTE_* (include/rdeic_hip.h)
+ROUTE_EDGE_IN8, ROUTE_EDGE_NARROW, ROUTE_HALO, ROUTE_SMALLC, ROUTE_DMA, ROUTE_TILE, ROUTE_DIRECT, \
+    ROUTE_MATERIALIZE = range(8)
+
+
 class GemmDesc(C.Structure):
     """Mirror of rdeic_gemm_desc (strided batched GEMM, train.hip)."""
     _fields_ = [
@@ -75,6 +85,7 @@ PROTOTYPES = {
     "rdeic_conv2d_up2_phases": (C.c_int, [C.POINTER(ConvDesc), _i64, _i32, _p]),
     "rdeic_conv2d_up2_group": (C.c_int, [C.POINTER(ConvDesc)]),
     "rdeic_conv2d_band_rows": (C.c_int, [C.POINTER(ConvDesc), _i32]),
+    "rdeic_conv2d_plan": (C.c_int, [C.POINTER(ConvDesc), _i32, C.POINTER(ConvPlan)]),
     "rdeic_prof_start": (C.c_int, [_i32, _i32]),
     "rdeic_prof_stop": (C.c_int, []),
     "rdeic_launch_count": (C.c_int64, [_i32]),

@@ -1,11 +1,13 @@
 // Shared definitions of the convolution / linear kernels (conv_gemm.hip: register-staged tiles, the tiny-cout
 // kernel, split-K reduce, dispatch and the C ABI; conv_dma.hip: the LDS-DMA implicit GEMM; conv_halo.hip: the
 // GroupNorm-fused 3x3 halo convs; conv_edge.hip: the VAE edge convs). Kernel arguments, the fused epilogues and
-// the LDS-DMA / wait helpers live here so the translation units compile in parallel.
+// the LDS-DMA / wait helpers live here so the translation units compile in parallel. Which kernel runs and how a
+// launch is sliced is host planning: conv_route.h / conv_route.cpp.
 #pragma once
 #include "common.h"
 #include "../../include/rdeic_hip.h"
 #include "prof.h"
+#include "conv_route.h"
 
 namespace rdeic_conv {
 
@@ -102,11 +104,7 @@ __device__ __forceinline__ uint4 gn_apply_chunk(uint4 raw, const float* ab, int 
 // output store are 16-byte coalesced vectors. Same fp32 operation order as the scalar epilogue
 // ((acc + bias) + emb -> act -> + res -> round), so results are bit-identical to it.
 // Needs BM/2 * (BN + 4) * 4 bytes of LDS; the caller has finished with its k-loop buffers.
-__host__ __device__ __forceinline__ bool epi_vec_ok(const ConvArgs& a) {
-  if (a.out_mode == 2) return (a.cout % 8) == 0 && (a.out_ld % 4) == 0 && ((uintptr_t)a.out % 8) == 0;
-  return a.out_mode == 0 && (a.cout % 8) == 0 && (a.out_ld % 8) == 0 && ((uintptr_t)a.out % 16) == 0 &&
-         (!a.res || ((a.res_ld % 8) == 0 && ((uintptr_t)a.res % 16) == 0));
-}
+// Whether it can run: epi_vec_ok (conv_route.h, shared with the planner).
 
 // Tile row -> output row (GEMM m) of the vector epilogue: the GEMM kernels' tiles are BM consecutive
 // rows from m0; the halo conv's tiles are image blocks whose 64-row wave rows are each contiguous.
@@ -552,35 +550,27 @@ __device__ __forceinline__ void wait_vm_rt(int n) {
   }
 }
 
-// process-wide switches (rdeic_set_conv_option / rdeic_set_conv_path), defined in conv_gemm.hip
-extern int g_conv_path, g_epi_vec, g_swz, g_force_tile, g_dma, g_halo, g_halo8, g_edge, g_up2_phases;
-extern int g_launch_limit;  // largest byte span one launch addresses (rdeic_set_conv_option(12, v)), <= 2^31 - 1
+// Kernel arguments of one slice of a single-input conv (halo, narrow): the whole conv's, on the slice's window.
+inline ConvArgs slice_args(const ConvArgs& a, const Slice& s) {
+  ConvArgs e = a;
+  e.n = s.d.n; e.h = s.d.h; e.ho = s.d.ho; e.pad_t = s.d.pad_t;
+  e.M = e.n * e.ho * e.wo;
+  e.in0 = (const char*)s.d.in0;
+  e.out = (char*)s.d.out;
+  e.res = (const char*)s.d.res;
+  e.emb = s.d.emb;
+  e.gn_ab = s.d.gn_ab;
+  e.gn_row0 = (int)s.gn_row0;
+  return e;
+}
 
-// ---- image groups and row bands (conv_dma.hip; host arithmetic) ----
-// The fast kernels address activations through 32-bit byte offsets. A launch over several images that exceeds
-// g_launch_limit runs as groups of whole images; one image that exceeds it runs as bands of output rows, each band
-// a launch of the same kernel over a row window of the input (h, pad_t) and of the output / residual (ho).
-long image_span(const rdeic_conv_desc* d);  // the largest of one image's input, output and residual byte spans
-// Output rows per band (a multiple of row_tile; with gn_part, of whole 64-row statistic blocks): ho when the image
-// fits, 0 when not even one row tile does.
-int band_rows(const rdeic_conv_desc* d, int row_tile);
-struct Band {
-  int r0, rows;   // output rows [r0, r0 + rows)
-  int i0, h;      // stored input rows [i0, i0 + h) the band reaches
-  int pad_t;      // rows of zero padding above input row i0 (0 for an interior band: it carries its upper rows)
-};
-Band band_at(const rdeic_conv_desc* d, int r0, int rows);
-
-// cross-unit entry points
+// cross-unit entry points: the launchers run what a plan of conv_route.cpp says (every slice already checked)
 int make_args(const rdeic_conv_desc* d, ConvArgs& a, bool& vec);                                     // conv_gemm.hip
-bool dma_ok(const rdeic_conv_desc* d, const ConvArgs& a, unsigned& b0, unsigned& b1, unsigned& bw);  // conv_dma.hip
 int launch_dma_auto(const ConvArgs& a, unsigned b0, unsigned b1, unsigned bw, hipStream_t s, int tile,
-                    int gn_hw = 0, bool* fused = nullptr);
-int dma_grouped(const rdeic_conv_desc* d, int tile, hipStream_t s, bool* fused = nullptr);
-bool halo_ok(const rdeic_conv_desc* d, const ConvArgs& a);                                          // conv_halo.hip
-int launch_halo(const rdeic_conv_desc* d, ConvArgs a, hipStream_t s, bool* fused);
-int launch_edge(const rdeic_conv_desc* d, const ConvArgs& a, hipStream_t s, bool* fused);  // conv_edge.hip
-int up2_phase_group(const rdeic_conv_desc* d);                                            // conv_dma.hip
-bool up2_phases_ok(const rdeic_conv_desc* d, long phase_stride);
-int launch_up2_phases(const rdeic_conv_desc* d, long phase_stride, int tile, hipStream_t s, bool* fused);
+                    int gn_hw = 0, bool* fused = nullptr);                                           // conv_dma.hip
+int launch_dma_plan(const rdeic_conv_desc* d, const Plan& p, int tile, hipStream_t s, bool* fused);
+int launch_up2_phases(const rdeic_conv_desc* d, const Plan& p, long phase_stride, int tile, hipStream_t s, bool* fused);
+int launch_halo(const rdeic_conv_desc* d, const Plan& p, ConvArgs a, hipStream_t s, bool* fused);    // conv_halo.hip
+int launch_conv_in8(const ConvArgs& a, hipStream_t s, bool* fused);                                  // conv_edge.hip
+int launch_narrow(const rdeic_conv_desc* d, const Plan& p, const ConvArgs& a, hipStream_t s);
 }  // namespace rdeic_conv

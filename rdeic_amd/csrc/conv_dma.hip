@@ -299,24 +299,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) __attribute__((amdgpu_num_sgpr(80))
   conv_dma_body<BM, BN, WGM, WGN, S, EP, GEG>(a, tiles_n, bytes0, bytes1, bytesw);
 }
 
-// DMA-path eligibility: bf16, 16-byte-aligned 64-channel blocks, every input span inside the launch limit.
-bool dma_ok(const rdeic_conv_desc* d, const ConvArgs& a, unsigned& b0, unsigned& b1, unsigned& bw) {
-  if (d->dtype != 1 || d->gn_ab || (d->c0 % 64) || (d->c1 % 64) || (d->ld0 % 8) || ((uintptr_t)d->in0 % 16)) return false;
-  if (d->c1 && ((d->ld1 % 8) || ((uintptr_t)d->in1 % 16))) return false;
-  if (d->wld % 64 || a.ktot % 64) return false;
-  const long pix = (long)d->n * d->h * d->w;
-  const long e0 = ((pix - 1) * d->ld0 + d->c0) * 2 + (a.batch - 1) * d->in_bs * 2;
-  const long e1 = d->c1 ? ((pix - 1) * d->ld1 + d->c1) * 2 : 16;
-  const long ew = (long)d->cout * d->wld * 2 + (a.batch - 1) * d->w_bs * 2;
-  if (e0 > g_launch_limit || e1 > g_launch_limit || ew >= (1l << 31)) return false;
-  if (a.batch > 1 && (d->in_bs % 8 || d->w_bs % 8)) return false;
-  // batched operands are addressed from the per-z base: the descriptor covers one slice
-  b0 = (unsigned)(((pix - 1) * d->ld0 + d->c0) * 2);
-  b1 = (unsigned)e1;
-  bw = (unsigned)((long)d->cout * d->wld * 2);
-  return true;
-}
-
 namespace {
 // Whether the kernel's vector epilogue runs for these arguments (the compile-time part mirrors the
 // `if constexpr` in conv_dma_body).
@@ -409,134 +391,23 @@ int launch_dma_auto(const ConvArgs& a, unsigned b0, unsigned b1, unsigned bw, hi
   }
 }
 
-// ---- image groups and row bands (conv_common.h) ----
-namespace {
-long gcd_l(long a, long b) { while (b) { const long t = a % b; a = b; b = t; } return a; }
-long lcm_l(long a, long b) { return a / gcd_l(a, b) * b; }
-// bytes of one stored input row / of one output row's pixels (the widest of the tensors addressed with them)
-long in_row_bytes(const rdeic_conv_desc* d) {
-  const long es = d->dtype == 0 ? 4 : 2;
-  const long ld = d->c1 && d->ld1 > d->ld0 ? d->ld1 : d->ld0;
-  return (long)d->w * ld * es;
-}
-long out_row_bytes(const rdeic_conv_desc* d) {
-  const long os = (d->out_f32 || d->dtype == 0) ? 4 : 2;
-  const long ld = d->res && d->res_ld > d->out_ld ? d->res_ld : d->out_ld;
-  return (d->out_mode == 1 ? 4l : 1l) * d->wo * ld * os;
-}
-}  // namespace
-
-long image_span(const rdeic_conv_desc* d) {
-  const long in = (long)d->h * in_row_bytes(d), out = (long)d->ho * out_row_bytes(d);
-  return in > out ? in : out;
-}
-
-int band_rows(const rdeic_conv_desc* d, int row_tile) {
-  if (d->h <= 0 || d->w <= 0 || d->ho <= 0 || d->wo <= 0 || d->ld0 <= 0 || d->out_ld <= 0) return 0;
-  const long lim = g_launch_limit;
-  if (image_span(d) <= lim) return d->ho;
-  const int kh = d->kh > 0 ? d->kh : 1, stride = d->stride > 0 ? d->stride : 1;
-  long step = row_tile > 1 ? row_tile : 1;
-  if (d->up2) step = lcm_l(step, 2);  // a band is whole source rows
-  if (d->gn_part) {                   // whole 64-row statistic blocks (up2: of each phase's source rows)
-    const long q = d->up2 ? 256 : 64;
-    step = lcm_l(step, q / gcd_l(d->wo, q));
+// The LDS-DMA kernel over the slices of a plan (conv_route.cpp: one launch, image groups or row bands; images
+// and output rows are independent in a conv, so the per-pixel arithmetic is the same and results are bit-identical).
+// *fused: false if any slice could not fuse the statistics; the caller then recomputes them.
+int launch_dma_plan(const rdeic_conv_desc* d, const Plan& p, int tile, hipStream_t s, bool* fused) {
+  for (int k = 0; k < p.launches; ++k) {
+    const Slice sl = slice_at(d, p, k);
+    ConvArgs ea;
+    bool vec = false;
+    unsigned b0, b1, bw;
+    make_args(&sl.d, ea, vec);
+    dma_ok(&sl.d, b0, b1, bw);
+    ea.gn_row0 = (int)sl.gn_row0;
+    bool f = false;
+    const int rc = launch_dma_auto(ea, b0, b1, bw, s, tile, d->gn_hw, &f);
+    if (rc != RDEIC_OK) return rc;
+    if (fused) *fused = (k == 0 ? f : (*fused && f));
   }
-  // a band of r output rows reaches at most (r - 1) * stride + kh stored input rows (up2, 3x3: r / 2 + 2)
-  const long in_rows = lim / in_row_bytes(d);
-  long r = d->up2 ? 2 * (in_rows - 2) : (in_rows - kh) / stride + 1;
-  if (in_rows < (d->up2 ? 3 : kh)) r = 0;
-  const long by_out = lim / out_row_bytes(d);
-  if (by_out < r) r = by_out;
-  r = r / step * step;
-  if (r < step) return 0;
-  return (int)(r < d->ho ? r : d->ho);  // full bands from row 0, the last one shorter
-}
-
-Band band_at(const rdeic_conv_desc* d, int r0, int rows) {
-  Band b;
-  b.r0 = r0;
-  b.rows = d->ho - r0 < rows ? d->ho - r0 : rows;
-  if (d->up2) {  // the phase launch: source rows [r0 / 2, (r0 + rows) / 2) and one row above and below
-    const int s0 = r0 / 2, ns = b.rows / 2;
-    b.i0 = s0 > 0 ? s0 - 1 : 0;
-    b.pad_t = 1 - (s0 - b.i0);
-    const int i1 = s0 + ns + 1 < d->h ? s0 + ns + 1 : d->h;
-    b.h = i1 - b.i0;
-    return b;
-  }
-  const int top = r0 * d->stride - d->pad_t;  // input row of the band's first tap row
-  b.i0 = top > 0 ? top : 0;
-  b.pad_t = b.i0 - top;
-  const int end = (r0 + b.rows - 1) * d->stride - d->pad_t + d->kh;
-  b.h = (end < d->h ? end : d->h) - b.i0;
-  return b;
-}
-
-// Images are independent in a conv, and so are output rows: a launch whose spans exceed the launch limit (the
-// 2 GiB reach of a 32-bit buffer offset) runs the DMA kernel over groups of images, or, where one image exceeds
-// it, over row bands of each image (out_mode 0, batch 1; same per-pixel arithmetic, bit-identical).
-// Returns -1 when the DMA path does not apply.
-int dma_grouped(const rdeic_conv_desc* d, int tile, hipStream_t s, bool* fused) {
-  ConvArgs a;
-  bool vec = false;
-  if (make_args(d, a, vec) != RDEIC_OK || !vec) return -1;
-  unsigned b0, b1, bw;
-  const bool whole = dma_ok(d, a, b0, b1, bw);
-  const long lim = g_launch_limit;
-  const long per = image_span(d);
-  if (whole && (d->batch > 1 || per * d->n <= lim)) return launch_dma_auto(a, b0, b1, bw, s, tile, d->gn_hw, fused);
-  if (d->batch > 1) return -1;
-  const int osz = (d->out_f32 || d->dtype == 0) ? 4 : 2;
-  const long ipix = (long)d->h * d->w;
-  const long per0 = ipix * d->ld0 * 2, per1 = d->c1 ? ipix * d->ld1 * 2 : 0;
-  if (per <= lim && d->n > 1) {  // the largest image group that fits
-    const int g = (int)(lim / per);
-    rdeic_conv_desc e = *d;
-    const long opix = d->out_mode == 1 ? 4l * d->ho * d->wo : (long)d->ho * d->wo;
-    for (int i0 = 0; i0 < d->n; i0 += g) {
-      e.n = d->n - i0 < g ? d->n - i0 : g;
-      e.in0 = (const char*)d->in0 + i0 * per0;
-      e.in1 = d->in1 ? (const char*)d->in1 + i0 * per1 : nullptr;
-      e.out = (char*)d->out + i0 * opix * d->out_ld * osz;
-      e.res = d->res ? (const char*)d->res + i0 * opix * d->res_ld * osz : nullptr;
-      e.emb = d->emb ? d->emb + (long)i0 * d->emb_ld : nullptr;
-      e.ln_rows = d->ln_rows ? d->ln_rows + 2l * i0 * d->ho * d->wo : nullptr;
-      ConvArgs ea;
-      if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return -1;
-      ea.gn_row0 = i0 * d->ho * d->wo;
-      bool f = false;
-      const int rc = launch_dma_auto(ea, b0, b1, bw, s, tile, d->gn_hw, &f);
-      if (rc != RDEIC_OK) return rc;
-      if (fused) *fused = (i0 == 0 ? f : (*fused && f));
-    }
-    return RDEIC_OK;  // *fused false if any group could not fuse: the caller recomputes the statistics
-  }
-  const int rows = (per > lim && d->out_mode == 0 && !d->up2 && d->dtype == 1) ? band_rows(d, 1) : 0;
-  if (rows <= 0 || rows >= d->ho) return whole ? launch_dma_auto(a, b0, b1, bw, s, tile, d->gn_hw, fused) : -1;
-  rdeic_conv_desc e = *d;
-  e.n = 1;
-  bool first = true;
-  for (int img = 0; img < d->n; ++img)
-    for (int r0 = 0; r0 < d->ho; r0 += rows) {
-      const Band b = band_at(d, r0, rows);
-      const long orow = ((long)img * d->ho + r0) * d->wo;  // first output pixel of the band
-      e.h = b.h; e.ho = b.rows; e.pad_t = b.pad_t;
-      e.in0 = (const char*)d->in0 + img * per0 + (long)b.i0 * d->w * d->ld0 * 2;
-      e.in1 = d->in1 ? (const char*)d->in1 + img * per1 + (long)b.i0 * d->w * d->ld1 * 2 : nullptr;
-      e.out = (char*)d->out + orow * d->out_ld * osz;
-      e.res = d->res ? (const char*)d->res + orow * d->res_ld * osz : nullptr;
-      e.emb = d->emb ? d->emb + (long)img * d->emb_ld : nullptr;
-      e.ln_rows = d->ln_rows ? d->ln_rows + 2 * orow : nullptr;
-      ConvArgs ea;
-      if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return first ? -1 : RDEIC_EINVAL;
-      ea.gn_row0 = (int)orow;
-      bool f = false;
-      const int rc = launch_dma_auto(ea, b0, b1, bw, s, tile, d->gn_hw, &f);
-      if (rc != RDEIC_OK) return rc;
-      if (fused) *fused = (first ? f : (*fused && f));
-      first = false;
-    }
   return RDEIC_OK;
 }
 
@@ -583,82 +454,24 @@ int launch_ph_auto(const ConvArgs& a, unsigned b0, unsigned b1, unsigned bw, hip
 }
 }  // namespace
 
-// Images per launch of the phase path: the largest group whose input span and (4x larger) output span both stay
-// inside the launch limit, evened out over the groups; 0 when one image already exceeds that (it runs as row bands).
-int up2_phase_group(const rdeic_conv_desc* d) {
-  const long ipix = (long)d->h * d->w;
-  const long per_in = ipix * d->ld0 * 2, per_out = 4 * ipix * d->out_ld * 2;
-  const long per = per_in > per_out ? per_in : per_out;
-  const long lim = g_launch_limit;
-  if (d->n <= 0 || per <= 0 || per > lim) return 0;
-  long g = lim / per;
-  if (g > d->n) g = d->n;
-  const long groups = (d->n + g - 1) / g;
-  return (int)((d->n + groups - 1) / groups);
-}
-
-bool up2_phases_ok(const rdeic_conv_desc* d, long phase_stride) {
-  if (!d || !d->in0 || !d->weight || !d->out || d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0) return false;
-  if (d->dtype != 1 || d->out_f32 || !d->up2 || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad_t != 1 ||
-      d->pad_l != 1 || d->ho != 2 * d->h || d->wo != 2 * d->w)
-    return false;
-  if (d->c1 || d->in1 || d->c0 <= 0 || d->c0 % 64 || d->out_mode != 0 || d->batch > 1) return false;
-  if (d->gn_ab || d->emb || d->res || d->ln_rows || d->ln_colsum) return false;
-  if (d->wld != 4 * d->c0 || phase_stride < (long)d->cout * d->wld || phase_stride % 8) return false;
-  if (d->ld0 < d->c0 || d->ld0 % 8 || ((uintptr_t)d->in0 % 16) || ((uintptr_t)d->weight % 16)) return false;
-  if (d->cout % 8 || d->out_ld < d->cout || d->out_ld % 8 || ((uintptr_t)d->out % 16)) return false;
-  if ((long)d->cout * d->wld * 2 >= (1l << 31)) return false;
-  return up2_phase_group(d) > 0 || band_rows(d, 1) > 0;
-}
-
-// -1: not eligible (nothing launched; the caller runs the fused-gather path)
-int launch_up2_phases(const rdeic_conv_desc* d, long phase_stride, int tile, hipStream_t s, bool* fused) {
-  if (!up2_phases_ok(d, phase_stride)) return -1;
-  const int g = up2_phase_group(d);
-  const long ipix = (long)d->h * d->w;
-  const long per_in = ipix * d->ld0 * 2, per_out = 4 * ipix * d->out_ld * 2;
-  rdeic_conv_desc e = *d;  // one phase: the 2x2 conv over the raw input, h x w GEMM rows per image
-  e.up2 = 0; e.kh = 2; e.kw = 2; e.stride = 1; e.pad_t = 1; e.pad_l = 1; e.ho = d->h; e.wo = d->w;
-  if (g == 0) {  // one image is past the launch limit: row bands of each image (band_at: source-row windows)
-    const int rows = band_rows(d, 1);
-    if (rows <= 0) return -1;
-    e.n = 1;
-    bool first = true;
-    for (int img = 0; img < d->n; ++img)
-      for (int r0 = 0; r0 < d->ho; r0 += rows) {
-        const Band b = band_at(d, r0, rows);
-        e.h = b.h; e.ho = b.rows / 2; e.pad_t = b.pad_t;
-        e.in0 = (const char*)d->in0 + img * per_in + (long)b.i0 * d->w * d->ld0 * 2;
-        e.out = (char*)d->out + img * per_out + (long)r0 * d->wo * d->out_ld * 2;
-        ConvArgs ea;
-        bool vec = false;
-        unsigned b0, b1, bw;
-        if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return first ? -1 : RDEIC_EINVAL;
-        ea.w_bs = phase_stride;
-        ea.img_h = d->h;
-        ea.gn_row0 = (int)(img * ipix + (long)(r0 / 2) * d->w);
-        bool f = false;
-        const int rc = launch_ph_auto(ea, b0, b1, bw, s, tile, &f);
-        if (rc != RDEIC_OK) return rc;
-        if (fused) *fused = (first ? f : (*fused && f));
-        first = false;
-      }
-    return RDEIC_OK;
-  }
-  for (int i0 = 0; i0 < d->n; i0 += g) {
-    e.n = d->n - i0 < g ? d->n - i0 : g;
-    e.in0 = (const char*)d->in0 + i0 * per_in;
-    e.out = (char*)d->out + i0 * per_out;
+// The phase launches over the slices of a plan (plan_up2_phases: evened-out image groups, or row bands of whole
+// source rows where one image is past the launch limit).
+int launch_up2_phases(const rdeic_conv_desc* d, const Plan& p, long phase_stride, int tile, hipStream_t s, bool* fused) {
+  for (int k = 0; k < p.launches; ++k) {
+    const Slice sl = slice_at(d, p, k);
+    const rdeic_conv_desc e = up2_phase_desc(sl.d);
     ConvArgs ea;
     bool vec = false;
     unsigned b0, b1, bw;
-    if (make_args(&e, ea, vec) != RDEIC_OK || !vec || !dma_ok(&e, ea, b0, b1, bw)) return i0 == 0 ? -1 : RDEIC_EINVAL;
+    make_args(&e, ea, vec);
+    dma_ok(&e, b0, b1, bw);
     ea.w_bs = phase_stride;
-    ea.gn_row0 = (int)(i0 * ipix);
+    ea.img_h = d->h;
+    ea.gn_row0 = (int)(sl.gn_row0 / 4);  // in source pixels: GEMM rows of one phase
     bool f = false;
     const int rc = launch_ph_auto(ea, b0, b1, bw, s, tile, &f);
     if (rc != RDEIC_OK) return rc;
-    if (fused) *fused = (i0 == 0 ? f : (*fused && f));
+    if (fused) *fused = (k == 0 ? f : (*fused && f));
   }
   return RDEIC_OK;
 }

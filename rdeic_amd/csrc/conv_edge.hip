@@ -186,7 +186,7 @@ __global__ __launch_bounds__(CI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 // after its transform). The transform is (TR + 2) / TR x 66 / 64 of the element count.
 // k order: 32-channel block major, tap minor (as the halo convs); fp32 accumulation.
 // ============================================================================================
-constexpr int NR_TC = 64, NR_HC = NR_TC + 2;
+constexpr int NR_TC = NARROW_TC, NR_HC = NR_TC + 2;  // 64 + 2
 template <int TR> struct Narrow {
   static constexpr int NT = TR * 64, HPIX = (TR + 2) * NR_HC, ITEMS = HPIX * 4;  // 16-byte chunks per halo
   static constexpr int IPT = (ITEMS + NT - 1) / NT;
@@ -332,82 +332,45 @@ __global__ __launch_bounds__(TR * 64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 
 }  // namespace
 
-int g_edge = 1;  // the edge kernels where they apply (rdeic_set_conv_option(10, v)): 1 on (default), 0 off
-
-namespace {
-// Image groups and row bands as launch_halo: every launch's input view (a 32-bit descriptor and offsets in the
-// kernel) and output view stay inside the launch limit.
-int launch_narrow(const rdeic_conv_desc* d, const ConvArgs& a, hipStream_t s) {
-  constexpr int TR = 8;
+// The narrow conv over the slices of a plan (conv_route.cpp, image groups and row bands as launch_halo): every
+// launch's input view (a 32-bit descriptor and offsets in the kernel) and output view stay inside the launch limit.
+int launch_narrow(const rdeic_conv_desc* d, const Plan& p, const ConvArgs& a, hipStream_t s) {
+  constexpr int TR = NARROW_TR;
+  static_assert(Narrow<TR>::LDS == NARROW_LDS, "the planner's LDS bound");
   const int lds = Narrow<TR>::LDS + d->c0 * 8 + d->cout * 9 * d->c0 * 2;
-  if (!(d->gn_ab && d->cout <= 16 && d->c0 % 32 == 0 && d->h % TR == 0 && d->w % NR_TC == 0 && lds <= 160 * 1024 &&
-        !d->gn_part && !d->emb && ((uintptr_t)d->gn_ab) % 16 == 0))
-    return -1;
-  const long ipix = (long)d->h * d->w;
-  const long lim = g_launch_limit, per = image_span(d);
-  const int g = per <= lim ? (int)(lim / per) : 1;  // images per launch
-  int rows = d->ho;                                  // output rows per launch
-  if (per > lim) {
-    rows = band_rows(d, TR);
-    if (rows <= 0) return -1;
+  for (int k = 0; k < p.launches; ++k) {
+    const ConvArgs e = slice_args(a, slice_at(d, p, k));
+    rdeic_count_launch(RDEIC_COUNT_EDGE);
+    const int tx = d->w / NR_TC, ty = e.ho / TR;
+    const dim3 gr((unsigned)((long)e.n * ty * tx));
+    if (d->gn_silu) hipLaunchKernelGGL((conv3x3_gn_narrow_kernel<TR, true>), gr, dim3(TR * 64), lds, s, e, tx, ty);
+    else hipLaunchKernelGGL((conv3x3_gn_narrow_kernel<TR, false>), gr, dim3(TR * 64), lds, s, e, tx, ty);
+    const int rc = launch_status();
+    if (rc != RDEIC_OK) return rc;
   }
-  const int osz = a.out_f32 ? 4 : 2;
-  for (int i0 = 0; i0 < d->n; i0 += g)
-    for (int r0 = 0; r0 < d->ho; r0 += rows) {
-      const Band bd = band_at(d, r0, rows);
-      const long opix = i0 * ipix + (long)r0 * d->w;  // first output pixel of the launch
-      ConvArgs e = a;
-      e.n = d->n - i0 < g ? d->n - i0 : g;
-      e.h = bd.h; e.ho = bd.rows; e.pad_t = bd.pad_t;
-      e.M = e.n * e.ho * d->wo;
-      e.in0 = a.in0 + (i0 * ipix + (long)bd.i0 * d->w) * d->ld0 * 2;
-      e.out = a.out + opix * d->out_ld * osz;
-      e.res = a.res ? a.res + opix * d->res_ld * osz : nullptr;
-      e.gn_ab = a.gn_ab + (long)i0 * d->c0 * 2;
-      rdeic_count_launch(RDEIC_COUNT_EDGE);
-      const int tx = d->w / NR_TC, ty = e.ho / TR;
-      const dim3 gr((unsigned)((long)e.n * ty * tx));
-      if (d->gn_silu) hipLaunchKernelGGL((conv3x3_gn_narrow_kernel<TR, true>), gr, dim3(TR * 64), lds, s, e, tx, ty);
-      else hipLaunchKernelGGL((conv3x3_gn_narrow_kernel<TR, false>), gr, dim3(TR * 64), lds, s, e, tx, ty);
-      const int rc = launch_status();
-      if (rc != RDEIC_OK) return rc;
-    }
   return RDEIC_OK;
 }
-}  // namespace
 
-// Returns -1 when neither edge kernel takes the launch.
-int launch_edge(const rdeic_conv_desc* d, const ConvArgs& a, hipStream_t s, bool* fused) {
-  if (!g_edge || d->dtype != 1 || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 ||
-      d->up2 || d->c1 || d->ho != d->h || d->wo != d->w || a.batch != 1 || d->out_mode != 0 || d->ld0 % 8 ||
-      ((uintptr_t)d->in0) % 16 || ((uintptr_t)d->weight) % 16)
-    return -1;
-  // conv_in: 8 input channels, bias only, bf16 output, statistics per image (64-row blocks)
-  if (d->c0 == 8 && !d->gn_ab && d->wld >= 128 && d->cout % 32 == 0 && d->cout <= 128 && d->w % 64 == 0 && !d->emb && !d->act && !d->res &&
-      !d->out_f32 && !d->ln_rows && d->out_ld % 8 == 0 && ((uintptr_t)d->out) % 16 == 0) {
-    // 16 bytes per pixel: no bands; an input past the kernel's 32-bit descriptor takes the general path
-    if ((long)a.M * d->ld0 * 2 > g_launch_limit) return -1;
-    ConvArgs e = a;
-    const bool stats = e.gn_part != nullptr && e.gn_hw > 0 && e.gn_hw % 64 == 0;
-    if (!stats) e.gn_part = nullptr;
-    if (fused) *fused = stats;
-    rdeic_count_launch(RDEIC_COUNT_EDGE);
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          cus <= 0)
-        cus = 256;
-    }
-    const int ntiles = e.M / 64;  // w % 64 == 0
-    const int lds = CJ_S * CJ_STAGE + 4 * CI_WLDS;
-    const int blocks = ntiles < 4 * cus ? ntiles : 4 * cus;  // four 4-wave blocks per CU
-    if (stats) hipLaunchKernelGGL(conv_in8_kernel<true>, dim3((unsigned)blocks), dim3(CI_NT), lds, s, e, ntiles);
-    else hipLaunchKernelGGL(conv_in8_kernel<false>, dim3((unsigned)blocks), dim3(CI_NT), lds, s, e, ntiles);
-    return launch_status();
+// conv_in: 8 input channels, bias only, bf16 output, statistics per image (64-row blocks)
+int launch_conv_in8(const ConvArgs& a, hipStream_t s, bool* fused) {
+  ConvArgs e = a;
+  const bool stats = e.gn_part != nullptr && e.gn_hw > 0 && e.gn_hw % 64 == 0;
+  if (!stats) e.gn_part = nullptr;
+  if (fused) *fused = stats;
+  rdeic_count_launch(RDEIC_COUNT_EDGE);
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+      cus = 256;
   }
-  // norm -> (SiLU) -> conv to <= 16 channels (table + weights in LDS beside the halo)
-  return launch_narrow(d, a, s);
+  const int ntiles = e.M / 64;  // w % 64 == 0
+  const int lds = CJ_S * CJ_STAGE + 4 * CI_WLDS;
+  const int blocks = ntiles < 4 * cus ? ntiles : 4 * cus;  // four 4-wave blocks per CU
+  if (stats) hipLaunchKernelGGL(conv_in8_kernel<true>, dim3((unsigned)blocks), dim3(CI_NT), lds, s, e, ntiles);
+  else hipLaunchKernelGGL(conv_in8_kernel<false>, dim3((unsigned)blocks), dim3(CI_NT), lds, s, e, ntiles);
+  return launch_status();
 }
 
 }  // namespace rdeic_conv

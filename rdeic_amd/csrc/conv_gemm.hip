@@ -22,16 +22,6 @@
 
 namespace rdeic_conv {
 
-int g_conv_path = 2;    // 0: 128-tiles with the fused GroupNorm prologue only, 2 (default): big-tile auto choice
-int g_epi_vec = 1;      // LDS-staged vector epilogue (rdeic_set_conv_option(0, v))
-int g_swz = 1;          // swizzled 128-B LDS rows where they win (1) / padded 144-B rows everywhere (0) (option 3)
-int g_force_tile = -1;  // >= 0: force launch_plain_auto's candidate (rdeic_set_conv_option(4, i)), tuning only
-int g_dma = 1;          // LDS-DMA path for cin % 64 == 0 (rdeic_set_conv_option(5, v))
-int g_halo = 1;         // 3x3 halo conv: 0 off, 1 for GroupNorm-input convs (default), 2 for every eligible conv
-int g_halo8 = 1;        // the 8-row halo conv where it applies (rdeic_set_conv_option(9, v))
-int g_up2_phases = 1;   // rdeic_conv2d_up2_phases runs the four folded 2x2 phase convs (rdeic_set_conv_option(11, v))
-int g_launch_limit = 0x7fffffff;  // largest activation byte span of one launch (rdeic_set_conv_option(12, v))
-
 namespace {
 
 // GNP: compile the GroupNorm+SiLU gather prologue in (false = plain gather, fewer VGPRs / VALU).
@@ -529,13 +519,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(ConvArgs a, const fl
 
 }  // namespace
 
-// descriptor -> kernel arguments (validation shared by rdeic_conv2d / rdeic_conv2d_splitk)
+// descriptor -> kernel arguments (validation and the vec rule: conv_route.cpp)
 int make_args(const rdeic_conv_desc* d, ConvArgs& a, bool& vec) {
-  if (!d || !d->in0 || !d->weight || !d->out) return RDEIC_EINVAL;
-  if (d->c0 <= 0 || d->c1 < 0 || (d->c1 > 0 && !d->in1) || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 ||
-      d->stride <= 0 || d->n <= 0 || d->ho <= 0 || d->wo <= 0)
-    return RDEIC_EINVAL;
-  if (d->dtype != 0 && d->dtype != 1) return RDEIC_EINVAL;
+  const int rc = validate_desc(d);
+  if (rc != RDEIC_OK) return rc;
   a.in0 = (const char*)d->in0; a.in1 = (const char*)(d->in1 ? d->in1 : d->in0);
   a.c0 = d->c0; a.c1 = d->c1; a.ld0 = d->ld0; a.ld1 = d->c1 ? d->ld1 : d->ld0;
   a.n = d->n; a.h = d->h; a.w = d->w; a.up2 = d->up2; a.img_h = d->h;
@@ -552,70 +539,37 @@ int make_args(const rdeic_conv_desc* d, ConvArgs& a, bool& vec) {
   a.splits = 1; a.kper = 0;
   a.gn_part = d->gn_part; a.gn_row0 = 0; a.gn_hw = d->gn_hw;
   a.ln_rows = d->ln_rows; a.ln_cs = d->ln_colsum;
-  if ((d->ln_rows != nullptr) != (d->ln_colsum != nullptr)) return RDEIC_EINVAL;
-  if (d->ln_rows && (d->dtype != 1 || d->batch > 1 || d->out_mode == 1 || d->gn_ab || ((uintptr_t)d->ln_colsum) % 16))
-    return RDEIC_EINVAL;
   a.M = d->n * d->ho * d->wo;
   a.batch = d->batch > 1 ? d->batch : 1;
   a.in_bs = d->in_bs; a.w_bs = d->w_bs; a.out_bs = d->out_bs;
-  if (a.batch > 1 && (d->res || d->emb || d->out_mode)) return RDEIC_EINVAL;
   a.cin = d->c0 + d->c1;
   a.ktot = d->kh * d->kw * a.cin;
   const int BK = d->dtype == 1 ? 64 : 32;
-  if (d->wld < a.ktot || d->wld % 64 != 0) return RDEIC_EINVAL;
   a.nk = (a.ktot + BK - 1) / BK;
-  if (d->out_mode < 0 || d->out_mode > 2) return RDEIC_EINVAL;
-  if (d->out_mode == 1 && (d->cout % 4 != 0)) return RDEIC_EINVAL;
-  if (d->out_mode == 2 && (d->dtype != 1 || d->cout % 8 || d->res || d->emb || d->act || d->out_f32 || d->gn_ab ||
-                           a.batch > 1 || d->out_ld % 4 || ((uintptr_t)d->out) % 8))
-    return RDEIC_EINVAL;
-  const int epc = d->dtype == 1 ? 8 : 4;
-  vec = (d->c0 % epc == 0) && (d->ld0 % epc == 0) && (((uintptr_t)d->in0) % 16 == 0);
-  if (d->c1) vec = vec && (d->c1 % epc == 0) && (d->ld1 % epc == 0) && (((uintptr_t)d->in1) % 16 == 0);
-  if (((uintptr_t)d->weight) % 16 != 0) return RDEIC_EINVAL;
+  vec = vec_ok(d);
   return RDEIC_OK;
 }
 }  // namespace rdeic_conv
 
 using namespace rdeic_conv;
 
-static int conv2d_run(const rdeic_conv_desc* d, void* stream, bool* fused) {
+// The one dispatch: launch what the plan says (conv_route.cpp: validation, route, slices, all checked before
+// anything launches). tile -2: rdeic_conv2d; >= -1: rdeic_conv2d_tile. d->gn_part travels to the launchers that
+// can fuse the statistics into their epilogue (edge, halo, LDS-DMA, register tiles), which report it in *fused.
+static int conv2d_dispatch(const rdeic_conv_desc* d, const Plan& p, int32_t tile, hipStream_t s, bool* fused) {
   ConvArgs a;
   bool vec = false;
-  const int rc = make_args(d, a, vec);
-  if (rc != RDEIC_OK) return rc;
-  float* const part = a.gn_part;
-  a.gn_part = nullptr;  // statistics fuse into the LDS-DMA (dma_grouped reads d) and big-tile register paths
-  hipStream_t s = (hipStream_t)stream;
-  {  // the VAE edge convs (conv_edge.hip): conv_in (8 input channels), norm -> SiLU -> conv to <= 16 channels
-    ConvArgs e = a;
-    e.gn_part = part;
-    const int rc2 = launch_edge(d, e, s, fused);
-    if (rc2 != -1) return rc2;
+  make_args(d, a, vec);
+  switch (p.route) {
+    case RDEIC_ROUTE_EDGE_IN8: return launch_conv_in8(a, s, fused);
+    case RDEIC_ROUTE_EDGE_NARROW: return launch_narrow(d, p, a, s);
+    case RDEIC_ROUTE_HALO: return launch_halo(d, p, a, s, fused);
+    case RDEIC_ROUTE_DMA: return launch_dma_plan(d, p, tile, s, fused);  // tiles outside 21 .. 38: its heuristic
+    case RDEIC_ROUTE_TILE: return launch_plain_auto(a, s, tile, fused);  // tiles outside 0 .. 10: its heuristic
+    default: break;
   }
-  if (d->out_mode == 2) {  // fused GEGLU exists in the LDS-DMA kernel's vector epilogue only
-    const int rc2 = vec ? dma_grouped(d, -1, s) : -1;
-    return rc2 == -1 ? RDEIC_EINVAL : rc2;
-  }
-
-  if (vec && g_halo && (d->gn_ab || g_halo == 2) && halo_ok(d, a)) {
-    a.gn_part = part;
-    const int rc2 = launch_halo(d, a, s, fused);
-    if (rc2 != -1) return rc2;
-    a.gn_part = nullptr;
-  }
-  if (d->dtype == 1 && vec && d->cout <= 4 && d->c0 % 32 == 0 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 &&
-      d->pad_l == 1 && !d->up2 && !d->c1 && d->out_mode == 0 && a.batch == 1 && d->ho == d->h && d->wo == d->w &&
-      g_conv_path != 0)
-    return launch_smallc(a, s);
-  if (d->dtype == 1 && vec && !d->gn_ab && d->cout > 32 && g_conv_path != 0) {
-    if (g_dma) {
-      const int rc2 = dma_grouped(d, -1, s, fused);
-      if (rc2 != -1) return rc2;
-    }
-    a.gn_part = part;
-    return launch_plain_auto(a, s, -1, fused);
-  }
+  a.gn_part = nullptr;  // no fused statistics on the routes below
+  if (p.route == RDEIC_ROUTE_SMALLC) return launch_smallc(a, s);
   if (d->dtype == 1) {
     if (d->cout <= 16) return launch_cfg<bf16, 128, 16, 4, 1>(a, vec, s);
     if (d->cout <= 32) return launch_cfg<bf16, 128, 32, 4, 1>(a, vec, s);
@@ -630,33 +584,6 @@ static int conv2d_run(const rdeic_conv_desc* d, void* stream, bool* fused) {
       return launch_cfg<float, 128, 128, 2, 2>(a, vec, s);
     return launch_cfg<float, 64, 64, 2, 2>(a, vec, s);
   }
-}
-
-// Explicit tile choice for the big-tile path (autotuning by the caller; every tile gives
-// bit-identical results). tile -1 = the built-in heuristic. Shapes outside the big-tile path
-// (GN prologue, cout <= 32, fp32, unaligned) ignore it and run exactly as rdeic_conv2d.
-static int conv2d_tile_run(const rdeic_conv_desc* d, int32_t tile, void* stream, bool* fused) {
-  ConvArgs a;
-  bool vec = false;
-  const int rc = make_args(d, a, vec);
-  if (rc != RDEIC_OK) return rc;
-  if (vec) {  // the VAE edge convs take their shapes whatever the table's tile
-    const int rc2 = launch_edge(d, a, (hipStream_t)stream, fused);
-    if (rc2 != -1) return rc2;
-  }
-  if (d->out_mode == 2) {
-    const int rc2 = vec ? dma_grouped(d, tile >= 20 ? tile : -1, (hipStream_t)stream) : -1;
-    return rc2 == -1 ? RDEIC_EINVAL : rc2;
-  }
-  if (d->dtype == 1 && vec && !d->gn_ab && d->cout > 32 && g_conv_path != 0) {
-    if (tile >= 20) {
-      const int rc2 = dma_grouped(d, tile, (hipStream_t)stream, fused);
-      if (rc2 != -1) return rc2;
-      tile = -1;
-    }
-    return launch_plain_auto(a, (hipStream_t)stream, tile, fused);
-  }
-  return conv2d_run(d, stream, fused);
 }
 
 static double conv_flops(const rdeic_conv_desc* d) {
@@ -681,15 +608,14 @@ static double conv_bytes(const rdeic_conv_desc* d) {
 // d->gn_part: the output's GroupNorm statistics in the partial format of rdeic_groupnorm_parts_ab,
 // fused into the epilogue where the launch allows it, else by a separate pass over the output.
 static int conv2d_impl(const rdeic_conv_desc* d, int32_t tile, void* stream) {
-  if (d && d->gn_part &&
-      (d->gn_hw <= 0 || d->gn_hw % 64 || d->batch > 1 || d->out_mode != 0 || (long)d->n * d->ho * d->wo % d->gn_hw))
-    return RDEIC_EINVAL;
+  Plan p;
+  int rc = plan_conv(d, tile, false, p);  // a rejected descriptor returns before anything is profiled or launched
+  if (rc != RDEIC_OK) return rc;
   bool fused = false;
-  int rc;
   {
     rdeic_prof_add_bytes(conv_bytes(d));
     ProfScope ps((hipStream_t)stream, RDEIC_PROF_CONV, conv_flops(d));
-    rc = tile == -2 ? conv2d_run(d, stream, &fused) : conv2d_tile_run(d, tile, stream, &fused);
+    rc = conv2d_dispatch(d, p, tile, (hipStream_t)stream, &fused);
   }
   if (rc != RDEIC_OK || !d->gn_part || fused) return rc;
   const long rows = (long)d->n * d->ho * d->wo;
@@ -740,7 +666,7 @@ static int conv2d_splitk_impl(const rdeic_conv_desc* d, int32_t splits, float* w
     ConvArgs pa;
     bool pv = false;
     unsigned b0, b1, bw;
-    if (make_args(&e, pa, pv) == RDEIC_OK && pv && dma_ok(&e, pa, b0, b1, bw)) {
+    if (make_args(&e, pa, pv) == RDEIC_OK && pv && dma_ok(&e, b0, b1, bw)) {
       pa.splits = splits; pa.kper = (pa.nk + splits - 1) / splits;
       if (launch_dma_auto(pa, b0, b1, bw, s, -1) == RDEIC_OK) {
         a.splits = splits;
@@ -794,7 +720,8 @@ extern "C" int rdeic_conv2d_up2_phases(const rdeic_conv_desc* d, int64_t phase_s
   if (!d) return RDEIC_EINVAL;
   if (!g_up2_phases || !g_dma || g_conv_path == 0) return 1;
   if (d->gn_part && (d->gn_hw <= 0 || d->gn_hw % 64 || (long)d->n * d->ho * d->wo % d->gn_hw)) return RDEIC_EINVAL;
-  if (!up2_phases_ok(d, phase_stride)) return 1;
+  Plan p;
+  if (!plan_up2_phases(d, phase_stride, p)) return 1;  // the layer, or one of its slices, is not eligible
   bool fused = false;
   int rc;
   {
@@ -802,40 +729,9 @@ extern "C" int rdeic_conv2d_up2_phases(const rdeic_conv_desc* d, int64_t phase_s
     const double pix = (double)d->n * d->h * d->w;
     rdeic_prof_add_bytes(2.0 * (pix * d->c0 + 4.0 * d->cout * d->wld + 4.0 * pix * d->cout));
     ProfScope ps((hipStream_t)stream, RDEIC_PROF_CONV, 2.0 * pix * 4.0 * d->c0 * d->cout * 4.0);
-    rc = launch_up2_phases(d, phase_stride, tile, (hipStream_t)stream, &fused);
+    rc = launch_up2_phases(d, p, phase_stride, tile, (hipStream_t)stream, &fused);
   }
-  if (rc == -1) return RDEIC_EINVAL;  // unreachable: up2_phases_ok covers the launch's conditions
   if (rc != RDEIC_OK || !d->gn_part || fused) return rc;
   return gn_rows_partial(d->out, (long)d->n * d->ho * d->wo, d->cout, d->out_ld, d->gn_hw, d->gn_part, 1,
                          (hipStream_t)stream);
-}
-
-// Images per launch of rdeic_conv2d_up2_phases for this descriptor (host arithmetic only).
-extern "C" int rdeic_conv2d_up2_group(const rdeic_conv_desc* d) { return d ? up2_phase_group(d) : 0; }
-
-// Output rows per band of this descriptor's image under the launch limit (host arithmetic only).
-extern "C" int rdeic_conv2d_band_rows(const rdeic_conv_desc* d, int32_t row_tile) { return d ? band_rows(d, row_tile) : 0; }
-
-extern "C" int rdeic_set_conv_path(int32_t path) {
-  int prev = g_conv_path;
-  g_conv_path = path;
-  return prev;
-}
-
-extern int rdeic_g_attn64;
-extern int rdeic_g_attn512;
-
-extern "C" int rdeic_set_conv_option(int32_t key, int32_t value) {
-  if (key == 0) { int prev = g_epi_vec; g_epi_vec = value; return prev; }
-  if (key == 1) { int prev = rdeic_g_attn64; rdeic_g_attn64 = value; return prev; }
-  if (key == 3) { int prev = g_swz; g_swz = value; return prev; }
-  if (key == 4) { int prev = g_force_tile; g_force_tile = value; return prev; }
-  if (key == 5) { int prev = g_dma; g_dma = value; return prev; }
-  if (key == 6) { int prev = g_halo; g_halo = value; return prev; }
-  if (key == 8) { int prev = rdeic_g_attn512; rdeic_g_attn512 = value; return prev; }
-  if (key == 9) { int prev = g_halo8; g_halo8 = value; return prev; }
-  if (key == 10) { int prev = g_edge; g_edge = value; return prev; }
-  if (key == 11) { int prev = g_up2_phases; g_up2_phases = value; return prev; }
-  if (key == 12) { int prev = g_launch_limit; g_launch_limit = value > 0 ? value : 0x7fffffff; return prev; }
-  return RDEIC_EINVAL;
 }

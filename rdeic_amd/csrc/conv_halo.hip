@@ -28,15 +28,15 @@ namespace rdeic_conv {
 // tile's 64-pixel wave rows mapped to their image rows.
 // ============================================================================================
 namespace halo {
-constexpr int TR = 4, TC = 64;            // output rows / columns per tile
+constexpr int TR = HALO_TR, TC = HALO_TC;  // output rows / columns per tile (4 x 64)
 constexpr int HR = TR + 2, HC = TC + 2;   // halo rows / columns
 constexpr int HPIX = HR * HC;             // 396 halo pixels
 constexpr int NPIECE = (HPIX * 4 + 63) / 64;  // 1 KB DMA pieces per halo (25)
 constexpr int HBYTES = NPIECE * 1024;     // one halo buffer (the last piece's tail slots read zeros)
-constexpr int BN = 128, NW = 8, NT = NW * 64;
+constexpr int BN = HALO_BN, NW = 8, NT = NW * 64;  // 128 output channels per tile
 constexpr int BBYTES = BN * 64;           // one tap's 32-channel weight slice
 constexpr int NB = 3;                     // weight ring depth
-constexpr int AB_MAX = 512;               // input channels whose GroupNorm affine fits the LDS table
+constexpr int AB_MAX = HALO_AB_MAX;       // input channels whose GroupNorm affine fits the LDS table
 constexpr int LDS = 2 * HBYTES + NB * BBYTES + AB_MAX * 8;
 static_assert(LDS <= 80 * 1024, "two blocks per CU");
 static_assert((TR * TC / 2) * (BN + 4) * 4 <= LDS, "epilogue parking (two passes)");
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // the 4-row kernel (channel block major, tap minor), so both give bit-identical outputs.
 // ============================================================================================
 namespace halo8 {
-constexpr int TR = 8, TC = 64;
+constexpr int TR = HALO8_TR, TC = HALO_TC;  // 8 x 64
 constexpr int HR = TR + 2, HC = TC + 2;            // 10 x 66 halo pixels
 constexpr int HPIX = HR * HC;                      // 660
 constexpr int NPIECE = (HPIX * 4 + 63) / 64;       // 42 pieces of 1 KB
@@ -674,48 +674,20 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
   HALO_STAMP(3);
 }
 
-bool halo_ok(const rdeic_conv_desc* d, const ConvArgs& a) {
-  return d->dtype == 1 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && !d->up2 &&
-         d->c1 == 0 && d->c0 % 32 == 0 && d->c0 <= halo::AB_MAX && d->cout % halo::BN == 0 && d->ho == d->h &&
-         d->wo == d->w && d->h % halo::TR == 0 && d->w % halo::TC == 0 && a.batch == 1 && d->out_mode == 0 &&
-         d->ld0 % 8 == 0 && ((uintptr_t)d->in0 % 16) == 0 && d->wld % 64 == 0 && epi_vec_ok(a) && a.epi_vec;
-}
-
-// The halo conv over image groups whose spans stay inside the launch limit (32-bit buffer offsets), or, where one
-// image exceeds it, over row bands of each image: the same kernel on a row window of the input (band_at: an
-// interior band carries its neighbour rows, only the image's own borders read the zero padding) and of the
-// output / residual. Bit-identical to one launch; -1 when not even one row tile fits.
-int launch_halo(const rdeic_conv_desc* d, ConvArgs a, hipStream_t s, bool* fused) {
+// The halo conv over the slices of a plan (conv_route.cpp: image groups whose spans stay inside the launch limit,
+// or, where one image exceeds it, row bands of each image): the same kernel on a row window of the input (band_at:
+// an interior band carries its neighbour rows, only the image's own borders read the zero padding) and of the
+// output / residual. Bit-identical to one launch.
+int launch_halo(const rdeic_conv_desc* d, const Plan& p, ConvArgs a, hipStream_t s, bool* fused) {
   using namespace halo;
   const long ipix = (long)d->h * d->w;
-  const long lim = g_launch_limit, per = image_span(d);
-  if ((long)d->cout * d->wld * 2 >= (1l << 31)) return -1;
   const bool fe = !a.out_f32 && !a.emb && a.act == 0;
-  const bool h8 = g_halo8 && fe && d->h % halo8::TR == 0;  // the 8-row, one-block-per-CU form
-  const int g = per <= lim ? (int)(lim / per) : 1;  // images per launch
-  int rows = d->ho;                                  // output rows per launch
-  if (per > lim) {
-    rows = band_rows(d, h8 ? halo8::TR : TR);
-    if (rows <= 0) return -1;
-  }
+  const bool h8 = halo8_form(d);  // the 8-row, one-block-per-CU form
   const bool stats = a.gn_part != nullptr && d->gn_hw == ipix;
   if (fused) *fused = stats;
   if (!stats) a.gn_part = nullptr;
-  const int osz = a.out_f32 ? 4 : 2;
-  for (int i0 = 0; i0 < d->n; i0 += g)
-  for (int r0 = 0; r0 < d->ho; r0 += rows) {
-    const Band bd = band_at(d, r0, rows);
-    const long opix = i0 * ipix + (long)r0 * d->w;  // first output pixel of the launch
-    ConvArgs e = a;
-    e.n = d->n - i0 < g ? d->n - i0 : g;
-    e.h = bd.h; e.ho = bd.rows; e.pad_t = bd.pad_t;
-    e.M = e.n * e.ho * d->wo;
-    e.in0 = a.in0 + (i0 * ipix + (long)bd.i0 * d->w) * d->ld0 * 2;
-    e.out = a.out + opix * d->out_ld * osz;
-    e.res = a.res ? a.res + opix * d->res_ld * osz : nullptr;
-    e.emb = a.emb ? a.emb + (long)i0 * a.emb_ld : nullptr;
-    e.gn_ab = a.gn_ab ? a.gn_ab + (long)i0 * d->c0 * 2 : nullptr;
-    e.gn_row0 = (int)opix;
+  for (int k = 0; k < p.launches; ++k) {
+    const ConvArgs e = slice_args(a, slice_at(d, p, k));
     const unsigned b0 = (unsigned)((((long)e.n * e.h * d->w - 1) * d->ld0 + d->c0) * 2);
     const unsigned bw = (unsigned)((long)d->cout * d->wld * 2);
     rdeic_count_launch(RDEIC_COUNT_HALO_CONV);

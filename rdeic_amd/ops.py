@@ -106,27 +106,6 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
     pass over the tensor. stats_hw: pixels per image of that GroupNorm (default ho*wo).
     ln_rows: [M, 2] fp32 (mean, rstd) of the raw input rows from layer_norm_rowstats, with p packed by
     ParamStore.conv_ln: the output is linear(LayerNorm(x)) (the LayerNorm folded into the GEMM)."""
-    if gn is not None and _gn_materialize(x, x2, p) and not _halo_eligible(x, x2, p, up2, pad_t, pad_l, out_hw,
-                                                                           geglu or pixel_shuffle, out) \
-            and not _edge_narrow_eligible(x, x2, p, up2, pad_t, pad_l, out_hw, geglu or pixel_shuffle or emb is not None):
-        # the big-tile conv path has no GroupNorm prologue (it is VALU-bound there): materialise the
-        # normalised (concatenated) input once with the vectorised, HBM-rate apply kernel instead
-        xin = torch.empty(x.shape[:3] + (p.cin,), dtype=x.dtype, device=x.device)
-        c0 = x.shape[3]
-        pend = getattr(gn, "_rdeic_pending", None)
-        if pend is not None and c0 % 8 == 0 and pix_ld(x) % 8 == 0 and x.data_ptr() % 16 == 0 and \
-                (x2 is None or (x2.shape[3] % 8 == 0 and pix_ld(x2) % 8 == 0 and x2.data_ptr() % 16 == 0)):
-            p0, pc0, p1, c1, n_, hw_, groups, eps, gamma, beta = pend
-            _launch(("gn_apply", float(2 * xin.numel() * xin.element_size()), None), "rdeic_groupnorm_parts_apply",
-                    p0.data_ptr(), pc0, _ptr(p1), c1, x.data_ptr(), pix_ld(x), _ptr(x2),
-                    pix_ld(x2) if x2 is not None else 0, n_, hw_, groups, float(eps), gamma.data_ptr(),
-                    beta.data_ptr(), int(gn_silu), gn.data_ptr(), xin.data_ptr(), pix_ld(xin), stream_ptr())
-            del gn._rdeic_pending
-        else:
-            group_norm_apply(x, gn, gn_silu, out=xin[..., :c0])
-            if x2 is not None:
-                group_norm_apply(x2, gn[:, c0:], gn_silu, out=xin[..., c0:])
-        x, x2, gn = xin, None, None
     n, h, w, c0 = x.shape
     ld0 = pix_ld(x)
     c1, ld1 = 0, 0
@@ -172,8 +151,7 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
     if gn is not None:
         if gn.shape != (n, p.cin, 2):
             raise ValueError("gn affine must be [n, cin, 2]")
-        _ab_ready(gn)
-        d.gn_ab = gn.data_ptr()
+        d.gn_ab = gn.data_ptr()  # (a deferred finalize runs below, once the route is known)
         d.gn_silu = int(gn_silu)
     if emb is not None:
         if emb.dtype != torch.float32 or emb.shape[0] != n or emb.stride(1) != 1:
@@ -206,12 +184,41 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
         if nf:  # 0: the image size is not a multiple of 64 pixels; the GroupNorm reads the tensor
             part = torch.empty(nf, dtype=torch.float32, device=x.device)
             d.gn_part, d.gn_hw = part.data_ptr(), ghw
+    # Which kernel family the library runs this on (rdeic_conv2d_plan: host arithmetic, not recorded into launch
+    # plans). tile -1: the route of rdeic_conv2d_tile, i.e. TILE for everything the tile table applies to.
+    route = _conv_plan(d).route
+    if route == _lib.ROUTE_MATERIALIZE:
+        # no fused-GroupNorm kernel takes it and the big-tile conv path has no GroupNorm prologue (it is VALU-bound
+        # there): materialise the normalised (concatenated) input once with the vectorised, HBM-rate apply kernel
+        xin = torch.empty(x.shape[:3] + (p.cin,), dtype=x.dtype, device=x.device)
+        pend = getattr(gn, "_rdeic_pending", None)
+        if pend is not None and c0 % 8 == 0 and pix_ld(x) % 8 == 0 and x.data_ptr() % 16 == 0 and \
+                (x2 is None or (x2.shape[3] % 8 == 0 and pix_ld(x2) % 8 == 0 and x2.data_ptr() % 16 == 0)):
+            p0, pc0, p1, pc1, n_, hw_, groups, eps, gamma, beta = pend
+            _launch(("gn_apply", float(2 * xin.numel() * xin.element_size()), None), "rdeic_groupnorm_parts_apply",
+                    p0.data_ptr(), pc0, _ptr(p1), pc1, x.data_ptr(), pix_ld(x), _ptr(x2),
+                    pix_ld(x2) if x2 is not None else 0, n_, hw_, groups, float(eps), gamma.data_ptr(),
+                    beta.data_ptr(), int(gn_silu), gn.data_ptr(), xin.data_ptr(), pix_ld(xin), stream_ptr())
+            del gn._rdeic_pending
+        else:
+            group_norm_apply(x, gn, gn_silu, out=xin[..., :c0])
+            if x2 is not None:
+                group_norm_apply(x2, gn[:, c0:], gn_silu, out=xin[..., c0:])
+        x, x2, gn = xin, None, None
+        c0, c1 = p.cin, 0
+        d.in0, d.in1, d.c0, d.c1, d.ld0, d.ld1 = x.data_ptr(), None, c0, 0, pix_ld(x), 0
+        d.gn_ab, d.gn_silu = None, 0
+        route = _conv_plan(d).route
+    _ab_ready(gn)
     flops = 2.0 * n * ho * wo * p.cout * p.kh * p.kw * p.cin
     splits = _splitk_count(x, x2, n * ho * wo, p, gn is not None or pixel_shuffle or geglu, out,
                            n if images is None else images)
 
     tile = -1
-    if splits == 1 and x.dtype == torch.bfloat16 and gn is None and _gn_materialize(x, x2, p):
+    # The tile table applies to the routes that take a tile. (Before the planner the lookup was keyed on the
+    # materialise rule: it also ran for conv_in shapes and cout <= 4 convs of 2^20 pixels, whose kernels ignore the
+    # tile, and skipped a GEGLU with cout <= 32, which no layer has. The same kernels run either way.)
+    if splits == 1 and gn is None and route in (_lib.ROUTE_DMA, _lib.ROUTE_TILE):
         key = tile_key(n * ho * wo, c0, c1, p, up2, d.out_mode, res is not None, emb is not None, act, odt)
         tile = TILE_TABLE.get(key, -1) if FORCE_TILE is None else FORCE_TILE
         if AUTOTUNE and FORCE_TILE is None and key not in TILE_TABLE:  # tuning runs only (tools/tune_tiles.py)
@@ -248,6 +255,13 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
     if part is not None:
         _attach_gn_part(out, part, d.gn_hw)
     return out
+
+
+def _conv_plan(d: ConvDesc, tile: int = -1) -> "_lib.ConvPlan":
+    """The library's plan for the descriptor under its current switches (rdeic_conv2d_plan; host arithmetic)."""
+    plan = _lib.ConvPlan()
+    _lib.check("rdeic_conv2d_plan", _lib.load().rdeic_conv2d_plan(C.byref(d), tile, C.byref(plan)))
+    return plan
 
 
 # Fused GroupNorm statistics (conv2d(stats=True) -> group_norm_ab): the partial sums travel as an
@@ -567,15 +581,10 @@ def conv_profile_breakdown(records):
     return out
 
 
-CONV_PATH = 2  # mirrors rdeic_set_conv_path (0: fused-GN 128-tiles everywhere, 2: big-tile auto choice)
-
-
 def set_conv_path(path: int) -> int:
-    global CONV_PATH
-    prev = CONV_PATH
-    CONV_PATH = int(path)
-    _lib.load().rdeic_set_conv_path(CONV_PATH)
-    return prev
+    """rdeic_set_conv_path: 0 the 128-tile kernel with the fused GroupNorm prologue everywhere, 2 (default) the
+    big-tile auto choice. Returns the previous value."""
+    return int(_lib.load().rdeic_set_conv_path(int(path)))
 
 
 def set_conv_option(key: int, value: int) -> int:
@@ -595,30 +604,13 @@ def set_launch_limit(nbytes: int) -> int:
     return set_conv_option(12, max(1, min(int(nbytes), LAUNCH_LIMIT_MAX)))
 
 
-def _band_plan_ok(x: torch.Tensor, p: "ConvParams", out, row_tile: int) -> bool:
-    """Whether the library's band planner (rdeic_conv2d_band_rows) has a plan for this 3x3 / stride-1 / pad-1 conv
-    under the launch limit: the whole image, or bands of row_tile rows; False = not even one row tile fits and the
-    halo / narrow kernels do not take the launch."""
-    n, h, w, _ = x.shape
-    d = ConvDesc()
-    d.n, d.h, d.w, d.ho, d.wo = n, h, w, h, w
-    d.c0, d.ld0, d.cout = x.shape[3], pix_ld(x), p.cout
-    d.kh, d.kw, d.stride, d.pad_t, d.pad_l = 3, 3, 1, 1, 1
-    d.out_ld = pix_ld(out) if out is not None else p.cout
-    d.dtype = 1
-    return int(_lib.load().rdeic_conv2d_band_rows(C.byref(d), row_tile)) > 0
-
-
 # 3x3 halo conv (rdeic_amd/csrc/conv_halo.hip, conv3x3_halo8_kernel / conv3x3_halo_kernel): a conv whose input is a
 # GroupNorm (+ SiLU) of a single 32-channel-aligned NHWC tensor and whose output tiles as 4 x 64 pixel
 # blocks x 128 channels takes the raw input and applies the affine once per element in LDS, instead
 # of materialising the normalised tensor (rdeic_set_conv_option(6, .): 0 off, 1 GroupNorm inputs, 2 all).
-HALO_CONV = 1
-# widest input / output the halo conv takes over from the materialised path: measured at B=16
-# (tools/halo_bench.py, r03) it wins on the 512^2 128-channel layers (2.14 -> 1.53 ms, 3.59 -> 2.62 ms)
-# and the 256^2 ones (0.86 -> 0.75, 1.39 -> 1.26 ms) and ties the 256x256 im2col tiles on the
-# 512-channel layers at 128^2 / 64^2 (where it still saves the GroupNorm apply launches)
-HALO_MAX_C = 512
+# The library decides where it runs (rdeic_conv2d_plan, route HALO).
+def set_halo_conv(mode: int) -> int:
+    return set_conv_option(6, mode)
 
 
 # launch counters of the library (rdeic_launch_count, RDEIC_COUNT_* in include/rdeic_hip.h)
@@ -644,74 +636,12 @@ def launch_count_reset() -> None:
     call("rdeic_launch_count_reset")
 
 
-def set_halo_conv(mode: int) -> int:
-    global HALO_CONV
-    prev = HALO_CONV
-    HALO_CONV = int(mode)
-    _lib.load().rdeic_set_conv_option(6, HALO_CONV)
-    return prev
-
-
-def _halo_eligible(x, x2, p: "ConvParams", up2, pad_t, pad_l, out_hw, special, out) -> bool:
-    """Mirror of the library's halo_ok (the conv2d_run dispatch) for a GroupNorm-input conv."""
-    if not HALO_CONV or x.dtype != torch.bfloat16 or x2 is not None or up2 or special:
-        return False
-    if p.kh != 3 or p.kw != 3 or p.stride != 1 or p.pad != 1 or (pad_t not in (None, 1)) or (pad_l not in (None, 1)):
-        return False
-    n, h, w, c = x.shape
-    if out_hw is not None and tuple(out_hw) != (h, w):
-        return False
-    if c % 32 or c > min(512, HALO_MAX_C) or p.cout > HALO_MAX_C or p.cout % 128 or h % 4 or w % 64 \
-            or x.stride(2) % 8 or x.data_ptr() % 16:
-        return False
-    if out is not None and (pix_ld(out) % 8 or out.data_ptr() % 16):
-        return False
-    return _band_plan_ok(x, p, out, 8 if h % 8 == 0 else 4)
-
-
 # The VAE edge convs (rdeic_amd/csrc/conv_edge.hip, rdeic_set_conv_option(10, .)): conv_in from 8 channels on
 # direct-load MFMA fragments, and norm -> SiLU -> 3x3 conv to <= 16 channels (the decoder's conv_out) with the
 # GroupNorm applied once per element in LDS instead of materialised (one read of the input instead of read + write
 # + read).
-EDGE_CONV = 1
-
-
 def set_edge_conv(mode: int) -> int:
-    global EDGE_CONV
-    prev = EDGE_CONV
-    EDGE_CONV = int(mode)
-    _lib.load().rdeic_set_conv_option(10, EDGE_CONV)
-    return prev
-
-
-def _edge_narrow_eligible(x, x2, p: "ConvParams", up2, pad_t, pad_l, out_hw, special) -> bool:
-    """Mirror of the library's launch_edge rule for the GroupNorm-input narrow conv."""
-    if not EDGE_CONV or x.dtype != torch.bfloat16 or x2 is not None or up2 or special:
-        return False
-    if p.kh != 3 or p.kw != 3 or p.stride != 1 or p.pad != 1 or (pad_t not in (None, 1)) or (pad_l not in (None, 1)):
-        return False
-    n, h, w, c = x.shape
-    if out_hw is not None and tuple(out_hw) != (h, w):
-        return False
-    lds = 10 * 66 * 64 + c * 8 + p.cout * 9 * c * 2  # 8-row halo, GroupNorm table, weights (conv_edge.hip)
-    return p.cout <= 16 and c % 32 == 0 and lds <= 160 * 1024 and h % 8 == 0 and w % 64 == 0 \
-        and x.stride(2) % 8 == 0 and x.data_ptr() % 16 == 0 and _band_plan_ok(x, p, None, 8)
-
-
-def _gn_materialize(x: torch.Tensor, x2: Optional[torch.Tensor], p: ConvParams) -> bool:
-    """Same rule as rdeic_conv2d's dispatch to the big-tile path (bf16, 16-byte gathers, cout > 32), plus
-    the large tiny-cout convs (the VAE's conv_out): their direct kernel would redo the GroupNorm + SiLU
-    of every input element for all 9 taps."""
-    if CONV_PATH == 0 or x.dtype != torch.bfloat16:
-        return False
-    if p.cout <= 32 and not (p.cout <= 4 and x.shape[0] * x.shape[1] * x.shape[2] >= (1 << 20)):
-        return False
-    for t in (x, x2):
-        if t is None:
-            continue
-        if t.shape[3] % 8 or t.stride(2) % 8 or t.data_ptr() % 16:
-            return False
-    return True
+    return set_conv_option(10, mode)
 
 
 def linear(x: torch.Tensor, p: ConvParams, *, act: int = NONE, res: Optional[torch.Tensor] = None,

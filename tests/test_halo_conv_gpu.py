@@ -34,7 +34,6 @@ def _gn_ab(x, groups, seed, eps=1e-6):
 def _run(x, p, ab, silu=True, res=None, stats=False, halo=True):
     from rdeic_amd import ops
     prev = ops.set_halo_conv(1 if halo else 0)
-    prev_c, ops.HALO_MAX_C = ops.HALO_MAX_C, 512  # every width the kernel supports, not only the ones it wins
     try:
         n0 = ops.launch_count(ops.COUNT_HALO_CONV)
         y = ops.conv2d(x, p, gn=ab, gn_silu=silu, res=res, stats=stats)
@@ -43,7 +42,6 @@ def _run(x, p, ab, silu=True, res=None, stats=False, halo=True):
         return y
     finally:
         ops.set_halo_conv(prev)
-        ops.HALO_MAX_C = prev_c
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout", [(2, 64, 128, 128, 128), (1, 32, 64, 256, 128), (2, 16, 64, 128, 256),
