@@ -646,7 +646,8 @@ int rdeic_act_bwd(const void* dy, int32_t ldy, const void* z, int32_t ldz, int64
                   float slope, void* dz, int32_t lddz, int32_t dtype, void* stream);
 /* GroupNorm training forward: mean / rstd per (image, group) -> mr [n][g][2] and the affine
  * ab [n][c][2] (apply with rdeic_groupnorm_apply); backward (+ SiLU when silu) -> dx, dgamma,
- * dbeta (null: not wanted). ws: rdeic_gn_train_ws_doubles; coef: [n][g][2] floats. */
+ * dbeta (null: not wanted; each on its own, unlike rdeic_layernorm_bwd's pair: the per-channel sums exist
+ * either way). ws: rdeic_gn_train_ws_doubles; coef: [n][g][2] floats. */
 size_t rdeic_gn_train_ws_doubles(int32_t n, int32_t hw, int32_t c);
 int rdeic_gn_train_fwd(const void* x, int32_t ldx, int32_t n, int32_t hw, int32_t c, int32_t groups, float eps,
                        const float* gamma, const float* beta, float* mr, float* ab, double* ws, int32_t dtype,
@@ -661,7 +662,8 @@ int rdeic_gn_train_bwd_res(const void* x, int32_t ldx, const void* dy, int32_t l
                            int32_t groups, const float* mr, const float* gamma, const float* beta, int32_t silu,
                            const void* dres, int32_t ldr, void* dx, int32_t lddx, float* dgamma, float* dbeta,
                            int32_t accumulate, double* ws, float* coef, int32_t dtype, void* stream);
-/* LayerNorm backward (statistics recomputed); dgamma / dbeta optional (ws then required) */
+/* LayerNorm backward (statistics recomputed); dgamma / dbeta optional (ws then required), but only as a
+ * pair: both or neither. Exactly one of them given returns RDEIC_EINVAL (-22) and launches nothing. */
 size_t rdeic_layernorm_bwd_ws_floats(int64_t rows, int32_t c);
 int rdeic_layernorm_bwd(const void* x, int32_t ldx, int64_t rows, int32_t c, const float* gamma, float eps,
                         const void* dy, int32_t ldy, void* dx, int32_t lddx, float* dgamma, float* dbeta,

@@ -1378,6 +1378,7 @@ extern "C" int rdeic_layernorm_bwd_res(const void* x, int32_t ldx, int64_t rows,
                                        int32_t lddx, float* dgamma, float* dbeta, int32_t accumulate, float* ws,
                                        size_t ws_floats, int32_t dtype, void* stream) {
   if (!x || !dy || !dx || !gamma || rows <= 0 || c <= 0 || c > 2048) return RDEIC_EINVAL;
+  if ((dgamma != nullptr) != (dbeta != nullptr)) return RDEIC_EINVAL;  // the parameter gradients come as a pair
   const bool pg = dgamma && dbeta;
   if (pg && (!ws || ws_floats < rdeic_layernorm_bwd_ws_floats(rows, c))) return RDEIC_ENOSPC;
   hipStream_t s = (hipStream_t)stream;
