@@ -476,6 +476,37 @@ int rdeic_dists_moments(const float* x, int32_t ldx, const float* y, int32_t ldy
 int rdeic_dists_score(const double* mom, const double* alpha, const double* beta, int32_t n, int32_t c,
                       int32_t accumulate, double* out, void* stream);
 
+/* ------------------------------------------------------------ FID / KID (fid.hip)
+ * The kernels around the fp32 InceptionV3 convs of the FID / KID feature tower (layer table, weights, chunking and
+ * the host-side scores: rdeic_amd/fid.py). All activations fp32 NHWC with a pixel stride; every offset is 64-bit;
+ * no kernel uses an atomic; every output element is one fixed-order sum, so results repeat bit for bit and do not
+ * depend on the batch.
+ * prep: uint8 RGB [n][h][w][3] -> fp32 [n][oh][ow][4] (16-byte aligned): v / 255, bilinear resize to oh x ow
+ * (align_corners = false, no antialiasing: torch's F.interpolate(mode="bilinear")), then 2 v - 1; channel 3 is zero.
+ * Per axis in fp32, scale = (float)in / (float)out: s = max((d + 0.5) * scale - 0.5, 0), i0 = floor(s),
+ * i1 = min(i0 + 1, in - 1), t = s - i0; row = (1 - tx) v[i0] + tx v[i1], out = (1 - ty) row0 + ty row1. An input
+ * already oh x ow comes out as exactly (v / 255) * 2 - 1. */
+int rdeic_fid_prep(const uint8_t* img, int32_t n, int32_t h, int32_t w, int32_t oh, int32_t ow, float* out,
+                   void* stream);
+/* pool, window k, stride s, symmetric padding p (2 p <= k), floor mode: out [n][(h+2p-k)/s+1][(w+2p-k)/s+1][c].
+ * mode RDEIC_POOL_MAX: padding counts as -inf (bit-exact; with p = 0 the bits of rdeic_maxpool2d);
+ * mode RDEIC_POOL_AVG: the taps inside the map added in row-major order in fp32, divided by their number
+ * (count_include_pad = false). c % 4 != 0 or unaligned operands take a scalar path. */
+#define RDEIC_POOL_MAX 0
+#define RDEIC_POOL_AVG 1
+int rdeic_pool2d(const float* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ld_in, int32_t k, int32_t s,
+                 int32_t p, int32_t mode, float* out, int32_t ld_out, void* stream);
+/* global average pool: x [n][hw][c] (pixel stride ld) -> out [n][c] fp32. Four pixel lanes add their pixels in
+ * index order in fp64, the lanes are added in lane order, the mean is divided in fp64 and rounded once. The order
+ * depends on (hw, c) only. n <= 65535. */
+int rdeic_global_avgpool(const float* x, int32_t ld, int32_t n, int64_t hw, int32_t c, float* out, void* stream);
+/* Set moments of features x [rows][c] fp32 (row stride ld): sum[c] and outer[c][c] = sum_k x_k x_k^T in fp64
+ * (+= what is there when accumulate). Products and sums are fp64 (an fp32 x fp32 product is exact there), rows
+ * added in index order; the upper triangle is computed in 64 x 64 tiles and mirrored: outer[i][j] and outer[j][i]
+ * hold the same bits. rows >= 1; c % 4 == 0, c <= 2048, ld % 4 == 0, x 16-byte aligned, else -22. */
+int rdeic_feat_moments(const float* x, int64_t rows, int32_t c, int32_t ld, int32_t accumulate, double* sum,
+                       double* outer, void* stream);
+
 /* ------------------------------------------------------------ host coders
  * Gaussian-conditional tables (compressai 1.2.4 GaussianConditional.update, precision 16).
  * pmf: [levels][pmf_ld] float32 pmf rows of length pmf_len[i] followed by the tail mass

@@ -6,6 +6,7 @@
         --upsample_to_original] [--save_intermediates] [--max_images N]
         [--lpips_backbone PATH [--lpips_lin PATH] [--lpips_net alex|vgg]]
         [--dists_weights PATH [--dists_backbone PATH]]
+        [--fid_inception PATH [--fid_patch 256] [--kid_subset_size 1000]]
         [--captions_file FILE.json --clip_vocab bpe_simple_vocab_16e6.txt.gz]
 
 What it keeps from the reference:
@@ -41,6 +42,11 @@ What differs, all forced by the offline image or by design:
   * --dists_weights PATH (alpha / beta; the VGG16 convs from --dists_backbone or from the same file) adds DISTS
     (rdeic_amd/dists.py) as a `dists` column after lpips, in the per-image line and in the averages; without the
     flag the table and the prints are what they were;
+  * --fid_inception PATH (the InceptionV3 state dict, torchvision names) adds the set-level scores: every
+    reconstruction and its original (the pair the per-image metrics see) go through the patch protocol (--fid_patch,
+    0 = whole images) and the feature tower (rdeic_amd/fid.py); the run ends with one `FID ... KID ... ± ...
+    (N patches)` line and writes fid_kid.csv (set, n_images, n_patches, fid, kid_mean, kid_std) beside metrics.csv,
+    which does not change;
   * noise comes from a CPU generator seeded per image (--seed + the image's index in sorted
     order), so results do not depend on how images are grouped into batches and micro-batches.
 """
@@ -227,6 +233,8 @@ def parse_args(argv=None) -> Namespace:
     p.add_argument("--dists_backbone", type=str, default="",
                    help="torchvision VGG16 state dict (or the lpips package's) for DISTS; empty = the convs are "
                         "read from --dists_weights (stage<k>.<i>.*)")
+    from rdeic_amd import fid as _fid
+    _fid.add_cli_flags(p)
     p.add_argument("--captions_file", type=str, default="",
                    help="JSON {image path relative to --input: caption}: per-image text conditioning with "
                         "classifier-free guidance against the \"\" embedding (needs the text tower and --clip_vocab)")
@@ -253,6 +261,7 @@ def parse_args(argv=None) -> Namespace:
     for what, path in (("--dists_weights", args.dists_weights), ("--dists_backbone", args.dists_backbone)):
         if path and not os.path.isfile(path):  # refused at start-up, before the model loads
             p.error(f"{what} {path} is not a file")
+    _fid.check_cli_flags(p, args)
     if args.fp16:
         print("[inference_partition] --fp16: the reduced-precision path computes in bf16 on MI355X "
               "(float16 autocast is not provided); same as --bf16", file=sys.stderr)
@@ -294,6 +303,10 @@ def main(argv=None) -> List[Dict]:
     if args.dists_weights:
         from rdeic_amd.dists import DISTS
         dists_model = DISTS(args.dists_weights, backbone=args.dists_backbone or None)
+    fid_run = None
+    if args.fid_inception:
+        from rdeic_amd import fid as _fid
+        fid_run = _fid.FidKid(_fid.InceptionV3(args.fid_inception), args.fid_patch)
     model = _load(args)
     captions: Optional[Dict[str, str]] = None
     if args.captions_file:
@@ -366,6 +379,8 @@ def main(argv=None) -> List[Dict]:
                     out = out.resize((m["orig_w"], m["orig_h"]), resample)
                 out.save(f"{prefix}.png")
                 vals = compute_metrics(np.array(out), orig if up else scaled, lpips_model, dists_model)
+                if fid_run is not None:  # the same pair the per-image metrics see
+                    fid_run.add(torch.from_numpy(np.array(out)), torch.from_numpy(orig if up else scaled))
                 records.append({"image": rel, "bpp": bpp, "scale": m["scale"], **vals})
                 if texts is not None:
                     records[-1]["caption"] = texts[k]
@@ -385,6 +400,12 @@ def main(argv=None) -> List[Dict]:
             v = np.array([r[k] for r in records], dtype=np.float64)
             print(f"Mean {k.upper()}: {np.nanmean(v) if np.isfinite(v).any() else float('nan'):.4f}")
         print(f"Metrics saved to {path}")
+    if fid_run is not None and fid_run.n_patches < 2:
+        print(f"FID / KID need at least 2 patches on each side, got {fid_run.n_patches}: fid_kid.csv not written")
+    elif fid_run is not None:
+        row = {"set": "all", **fid_run.result(kid_subset_size=args.kid_subset_size)}
+        print(_fid.summary_line(row))
+        _fid.write_csv([row], os.path.join(args.output, "fid_kid.csv"))
     return records
 
 

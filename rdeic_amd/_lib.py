@@ -162,6 +162,11 @@ PROTOTYPES = {
     "rdeic_dists_moments_ws_doubles": (_sz, [_i32, _i64, _i32]),
     "rdeic_dists_moments": (C.c_int, [_p, _i32, _p, _i32, _i32, _i64, _i32, _p, _sz, _p, _p]),
     "rdeic_dists_score": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p]),
+    # FID / KID (fid.hip)
+    "rdeic_fid_prep": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "rdeic_pool2d": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p]),
+    "rdeic_global_avgpool": (C.c_int, [_p, _i32, _i32, _i64, _i32, _p, _p]),
+    "rdeic_feat_moments": (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p, _p]),
     "rdeic_groupnorm_parts_floats": (C.c_size_t, [_i64, _i32, _i32]),
     "rdeic_groupnorm_parts_ab": (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _i32, _f, _p, _p, _p, _p]),
     "rdeic_groupnorm_parts_apply": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _f, _p, _p,

@@ -62,6 +62,13 @@ def dists(pred_u8: torch.Tensor, target_u8: torch.Tensor, model) -> np.ndarray:
     return model(pred_u8, target_u8)
 
 
+def fid_kid(pred_u8_batches, target_u8_batches, tower, patch: int = 256, **kw) -> dict:
+    """FID and KID between reconstructions and originals (matching iterables of uint8 [n,H,W,3] batches) through
+    the patch protocol; tower: an rdeic_amd.fid.InceptionV3. Keys: n_images, n_patches, fid, kid_mean, kid_std."""
+    from . import fid as _fid
+    return _fid.fid_kid(pred_u8_batches, target_u8_batches, tower, patch=patch, **kw)
+
+
 # ------------------------------------------------------------------ no-reference metrics (NIQE, BRISQUE)
 # The reference's experiments/run_ood.py:93-127 scores reconstructions with pyiqa "niqe" / "brisque". pyiqa and its
 # model files are not in this image: the published algorithms (Mittal, Soundararajan, Bovik 2013; Mittal, Moorthy,

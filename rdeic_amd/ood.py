@@ -100,9 +100,10 @@ def score_image(pred: torch.Tensor, target: torch.Tensor, lpips=None, niqe_model
 def run_domain(model, files: Sequence[str], context: torch.Tensor, domain: str = "", cache_dir: str = "encodings/ood",
                sampler: str = "ddpm", steps: int = 2, guidance_scale: float = 1.0, latent_noise_std: float = 0.0,
                num_noise_samples: int = 1, seed: int = 231, batch_size: int = 1, lpips=None, niqe_model=None,
-               brisque_model=None, recon_dir: Optional[str] = None, dists=None) -> List[Dict]:
+               brisque_model=None, recon_dir: Optional[str] = None, dists=None, fid=None) -> List[Dict]:
     """One domain's images through the codec; one record per image (COLUMNS, and `dists` with a DISTS model), in
-    sorted file order. The best-of-N candidate is chosen on LPIPS alone."""
+    sorted file order. The best-of-N candidate is chosen on LPIPS alone. fid: an rdeic_amd.fid.FidKid that takes
+    every scored (reconstruction, original) pair; the records do not change with it."""
     from PIL import Image
     del guidance_scale  # no unconditional branch in the reference's call: no effect there either
     files = sorted(files)
@@ -175,6 +176,8 @@ def run_domain(model, files: Sequence[str], context: torch.Tensor, domain: str =
                            "bpp": 8.0 * os.path.getsize(os.path.join(stream_dir, stem)) / (H * W)}
                     rec.update(score_image(pred, torch.from_numpy(orig[None]).to(dev), lpips, niqe_model,
                                            brisque_model, dists=dists))
+                    if fid is not None:
+                        fid.add(pred, torch.from_numpy(orig[None]).to(dev))
                     if recon_dir:
                         Image.fromarray(pred[0].cpu().numpy()).save(os.path.join(recon_dir, f"{stem}.png"))
                     done[f] = rec

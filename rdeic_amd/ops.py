@@ -93,7 +93,7 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, out_f32: bool = False, pixel_shuffle: bool = False,
            geglu: bool = False, stats: bool = False, stats_hw: Optional[int] = None,
            images: Optional[int] = None, ln_rows: Optional[torch.Tensor] = None,
-           phases: Optional[ConvParams] = None) -> torch.Tensor:
+           phases: Optional[ConvParams] = None, splits: Optional[int] = None) -> torch.Tensor:
     """out = act(conv(cat(x, x2)) + bias + emb) + res   (all NHWC).
     phases (with up2): the layer's folded 2x2 phase weights (ParamStore.conv_up2_phases); the conv then runs as
     four phase convs in one launch (4/9 of the MACs) where the library takes it (UP2_PHASES, bf16, no
@@ -105,7 +105,10 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
     epilogue where the tile allows, rdeic_conv_desc.gn_part) and group_norm_ab(out) then needs no
     pass over the tensor. stats_hw: pixels per image of that GroupNorm (default ho*wo).
     ln_rows: [M, 2] fp32 (mean, rstd) of the raw input rows from layer_norm_rowstats, with p packed by
-    ParamStore.conv_ln: the output is linear(LayerNorm(x)) (the LayerNorm folded into the GEMM)."""
+    ParamStore.conv_ln: the output is linear(LayerNorm(x)) (the LayerNorm folded into the GEMM).
+    splits: the split-K count, whatever the thread's split-K switches say (1 = none); a caller that fixes it per
+    layer keeps the k grouping, and so every output bit, independent of the batch. A layer rdeic_conv2d_splitk does
+    not take (cout % 8, out_ld % 8, 16-byte gathers) raises. None: the rule of _splitk_count."""
     n, h, w, c0 = x.shape
     ld0 = pix_ld(x)
     c1, ld1 = 0, 0
@@ -211,8 +214,10 @@ def conv2d(x: torch.Tensor, p: ConvParams, *, x2: Optional[torch.Tensor] = None,
         route = _conv_plan(d).route
     _ab_ready(gn)
     flops = 2.0 * n * ho * wo * p.cout * p.kh * p.kw * p.cin
-    splits = _splitk_count(x, x2, n * ho * wo, p, gn is not None or pixel_shuffle or geglu, out,
-                           n if images is None else images)
+    if splits is None:
+        splits = _splitk_count(x, x2, n * ho * wo, p, gn is not None or pixel_shuffle or geglu, out,
+                               n if images is None else images)
+    splits = max(1, int(splits))
 
     tile = -1
     # The tile table applies to the routes that take a tile. (Before the planner the lookup was keyed on the

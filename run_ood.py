@@ -5,6 +5,7 @@
         [--save_recon] [--seed 231] [--ckpt FILE] [--dtype fp32|bf16] [--batch_size 1]
         [--lpips_backbone PATH [--lpips_lin PATH]] [--niqe_model FILE] [--brisque_model FILE]
         [--dists_weights PATH [--dists_backbone PATH]]
+        [--fid_inception PATH [--fid_patch 256] [--kid_subset_size 1000]]
 
 Per domain folder: pad to x64 -> compress to `<cache_dir>/<domain>/<stem>` -> decompress from that file -> relay
 decode -> crop -> score against the original (rdeic_amd/ood.py). Writes `<output_dir>/ood_results_<domain>.csv` per
@@ -19,6 +20,10 @@ Differences from the reference, all forced by the offline image or by design:
   * --dists_weights PATH (alpha / beta; the VGG16 convs from --dists_backbone or from the same file) adds DISTS
     (rdeic_amd/dists.py) as a `dists` column after lpips; without the flag the tables are what they were. The
     best-of-N candidate is still chosen on LPIPS;
+  * --fid_inception PATH (the InceptionV3 state dict, torchvision names) scores the sets, not the images: every
+    reconstruction and its original go through the patch protocol (--fid_patch, 0 = whole images) and the feature
+    tower (rdeic_amd/fid.py); `<output_dir>/fid_kid.csv` gets one row per domain and one row `all` (set, n_images,
+    n_patches, fid, kid_mean, kid_std). The other tables do not change;
   * noise comes from a CPU generator seeded per image (--seed + the image's index in its domain's sorted order), so
     results do not depend on --batch_size.
 """
@@ -68,7 +73,10 @@ def parse_args(argv=None) -> Namespace:
     p.add_argument("--dists_backbone", type=str, default="",
                    help="torchvision VGG16 state dict (or the lpips package's) for DISTS; empty = the convs are "
                         "read from --dists_weights (stage<k>.<i>.*)")
+    from rdeic_amd import fid as _fid
+    _fid.add_cli_flags(p)
     args = p.parse_args(argv)
+    _fid.check_cli_flags(p, args)
     if args.lpips_backbone and not args.lpips_lin:
         args.lpips_lin = os.path.join(".", "weight", "lpips", "alex.pth")
     if args.dists_backbone and not args.dists_weights:
@@ -106,6 +114,11 @@ def main(argv=None) -> List[Dict]:
     if args.dists_weights:
         from rdeic_amd.dists import DISTS
         dists_model = DISTS(args.dists_weights, backbone=args.dists_backbone or None)
+    fid_tower, fid_rows, fid_all = None, [], None
+    if args.fid_inception:
+        from rdeic_amd import fid as _fid
+        fid_tower = _fid.InceptionV3(args.fid_inception)
+        fid_all = _fid.FidKid(fid_tower, args.fid_patch)
     niqe_model = metrics.NIQE(args.niqe_model) if args.niqe_model else None
     brisque_model = metrics.BRISQUE(args.brisque_model) if args.brisque_model else None
     model = load_model(args.ckpt, args.dtype)
@@ -123,12 +136,19 @@ def main(argv=None) -> List[Dict]:
             continue
         files = list_image_files(domain_path)
         print(f"Found {len(files)} images")
+        fid_run = _fid.FidKid(fid_tower, args.fid_patch) if fid_tower is not None else None
         records = ood.run_domain(
             model, files, ctx, domain=name, cache_dir=args.cache_dir, sampler=args.sampler, steps=args.steps,
             guidance_scale=args.guidance_scale, latent_noise_std=args.latent_noise_std,
             num_noise_samples=args.num_noise_samples, seed=args.seed, batch_size=args.batch_size, lpips=lpips_model,
             niqe_model=niqe_model, brisque_model=brisque_model,
-            recon_dir=os.path.join(args.output_dir, name) if args.save_recon else None, dists=dists_model)
+            recon_dir=os.path.join(args.output_dir, name) if args.save_recon else None, dists=dists_model,
+            fid=fid_run)
+        if fid_run is not None:
+            fid_all.merge(fid_run)
+            if fid_run.n_patches >= 2:  # a domain with fewer patches has no covariance: it counts in `all` only
+                fid_rows.append({"set": name, **fid_run.result(kid_subset_size=args.kid_subset_size)})
+                print(f"{name}: " + _fid.summary_line(fid_rows[-1]))
         if records:
             path = os.path.join(args.output_dir, f"ood_results_{name}.csv")
             ood.write_csv(records, path, dists_model is not None)
@@ -139,6 +159,12 @@ def main(argv=None) -> List[Dict]:
         ood.write_csv(all_records, path, dists_model is not None)
         print(f"\nConsolidated results saved to {path}")
         print_summary(all_records, dists_model is not None)
+    if fid_all is not None and fid_all.n_patches < 2:
+        print(f"FID / KID need at least 2 patches on each side, got {fid_all.n_patches}: fid_kid.csv not written")
+    elif fid_all is not None:
+        fid_rows.append({"set": "all", **fid_all.result(kid_subset_size=args.kid_subset_size)})
+        print(_fid.summary_line(fid_rows[-1]))
+        _fid.write_csv(fid_rows, os.path.join(args.output_dir, "fid_kid.csv"))
     return all_records
 
 
