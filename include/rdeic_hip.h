@@ -544,6 +544,15 @@ int rdeic_rans_decode(void* handle, const int32_t* idx, size_t n, const int32_t*
 int rdeic_rans_decode_batch(int32_t count, void** handles, const int32_t* idx, size_t n_per, size_t stride,
                             const int32_t* cdf, int32_t cdf_ld, const int32_t* cdf_len, const int32_t* offset,
                             int32_t levels, int32_t* out, int32_t threads);
+/* The same step with one status per stream (status[count], in and out): a stream with a null handle
+ * or a nonzero status on entry is skipped (a stream that failed in an earlier stage stays failed);
+ * every other stream is decoded and its own return code (0, -EBADMSG, -EINVAL) is written to
+ * status[i]. The n_per symbols of every skipped or failed stream are written as 0. Returns 0 unless
+ * the call's own arguments are invalid: one bad stream does not fail the batch. */
+int rdeic_rans_decode_batch_status(int32_t count, void** handles, const int32_t* idx, size_t n_per, size_t stride,
+                                   const int32_t* cdf, int32_t cdf_ld, const int32_t* cdf_len,
+                                   const int32_t* offset, int32_t levels, int32_t* out, int32_t threads,
+                                   int32_t* status);
 void rdeic_rans_dec_close(void* handle);
 
 /* torchac 0.9.3-compatible binary arithmetic coder for a shared int16 CDF row of length lp

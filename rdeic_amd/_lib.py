@@ -178,6 +178,7 @@ PROTOTYPES = {
     "rdeic_rans_dec_open": (_p, [_p, _sz]),
     "rdeic_rans_decode": (C.c_int, [_p, _p, _sz, _p, _i32, _p, _p, _i32, _p]),
     "rdeic_rans_decode_batch": (C.c_int, [_i32, _p, _p, _sz, _sz, _p, _i32, _p, _p, _i32, _p, _i32]),
+    "rdeic_rans_decode_batch_status": (C.c_int, [_i32, _p, _p, _sz, _sz, _p, _i32, _p, _p, _i32, _p, _i32, _p]),
     "rdeic_rans_dec_close": (None, [_p]),
     "rdeic_ac_encode": (C.c_int, [_p, _sz, _p, _i32, _p, _sz, C.POINTER(_sz)]),
     "rdeic_ac_decode": (C.c_int, [_p, _sz, _sz, _p, _i32, _p]),

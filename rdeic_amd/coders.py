@@ -192,15 +192,26 @@ class RansDecoder:
 
 
 def rans_decode_batch(decoders: Sequence[RansDecoder], indexes: np.ndarray, t: GaussianTables,
-                      out: np.ndarray = None, threads: int = None) -> np.ndarray:
-    """indexes [count, n] -> symbols [count, n]; decoder i consumes row i."""
+                      out: np.ndarray = None, threads: int = None, status: np.ndarray = None) -> np.ndarray:
+    """indexes [count, n] -> symbols [count, n]; decoder i consumes row i.
+    status: int32 [count], in and out (rdeic_rans_decode_batch_status). Stream i is skipped when
+    decoders[i] is None or status[i] != 0; otherwise its own return code lands in status[i] and the
+    call does not raise for it. Rows of skipped and failed streams are all 0."""
     idx = np.ascontiguousarray(indexes, dtype=np.int32)
     count, n = idx.shape
     if out is None:
         out = np.empty((count, n), dtype=np.int32)
-    handles = (C.c_void_p * count)(*[d.handle for d in decoders])
-    call("rdeic_rans_decode_batch", count, C.cast(handles, C.c_void_p), _np_ptr(idx), n, n, _np_ptr(t.cdf), t.cdf_ld,
-         _np_ptr(t.cdf_length), _np_ptr(t.offset), t.levels, _np_ptr(out), threads or default_threads())
+    if status is None:
+        handles = (C.c_void_p * count)(*[d.handle for d in decoders])
+        call("rdeic_rans_decode_batch", count, C.cast(handles, C.c_void_p), _np_ptr(idx), n, n, _np_ptr(t.cdf),
+             t.cdf_ld, _np_ptr(t.cdf_length), _np_ptr(t.offset), t.levels, _np_ptr(out), threads or default_threads())
+        return out
+    if status.dtype != np.int32 or status.shape != (count,) or not status.flags.c_contiguous:
+        raise ValueError("status must be a contiguous int32 array of one entry per decoder")
+    handles = (C.c_void_p * count)(*[None if d is None else d.handle for d in decoders])
+    call("rdeic_rans_decode_batch_status", count, C.cast(handles, C.c_void_p), _np_ptr(idx), n, n, _np_ptr(t.cdf),
+         t.cdf_ld, _np_ptr(t.cdf_length), _np_ptr(t.offset), t.levels, _np_ptr(out), threads or default_threads(),
+         _np_ptr(status))
     return out
 
 

@@ -27,12 +27,12 @@ recorded once per shape as a launch plan and replayed (rdeic_amd/plan.py).
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import coders, ops
+from . import _lib, coders, ops
 from .params import ParamStore
 from .plan import PlanCache, host_step
 
@@ -412,7 +412,11 @@ class Compression:
 
                 def decode():
                     ready.synchronize()
-                    coders.rans_decode_batch(self._io["decs"][b0:b1], idx_p.numpy(), self.tables, out=sym_p.numpy())
+                    # isolate=True: a per-stream status instead of one exception for the batch; the failed and
+                    # the absent streams' symbols are written as 0, so the dequant below reads host-written rows
+                    st = self._io.get("status")
+                    coders.rans_decode_batch(self._io["decs"][b0:b1], idx_p.numpy(), self.tables, out=sym_p.numpy(),
+                                             status=None if st is None else st[b0:b1])
 
                 host_step(decode)
                 ops.call("rdeic_ckbd_dequant", sym_p.data_ptr(), params.data_ptr(), ops.pix_ld(params), nb, hy, wy, c,
@@ -427,32 +431,75 @@ class Compression:
         c_latent = ops.conv2d(guide_hint, self.store.conv(self.p + "out"), out_f32=True)
         return c_latent, guide_hint
 
-    @torch.no_grad()
-    def decompress(self, strings_list: Sequence[Sequence[Sequence[bytes]]], shape: Tuple[int, int],
-                   device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
-        """strings_list[b] = [[y_string], [z_string]] for image b (all of one latent shape).
-        Returns (c_latent fp32 NHWC [B,h,w,4], guide_hint NHWC [B,h,w,M]) (compression.py:215-273)."""
-        self.update()
-        B = len(strings_list)
+    @staticmethod
+    def check_z_shape(shape) -> Tuple[int, int]:
+        """The header's hyper-latent shape as ints; ValueError when no image can have it."""
         hz, wz = int(shape[0]), int(shape[1])
         if not (0 < hz <= 1024 and 0 < wz <= 1024 and hz * wz <= 65536):  # a 16384^2 image has a 256^2 z
             raise ValueError(f"implausible hyper-latent shape {(hz, wz)} (corrupted header?)")
-        zi = np.stack([coders.ac_decode_uniform(st[1][0], hz * wz, self.codebook_size) for st in strings_list])
+        return hz, wz
+
+    @torch.no_grad()
+    def decompress(self, strings_list: Sequence[Sequence[Sequence[bytes]]], shape: Tuple[int, int],
+                   device="cuda", isolate: bool = False):
+        """strings_list[b] = [[y_string], [z_string]] for image b (all of one latent shape).
+        Returns (c_latent fp32 NHWC [B,h,w,4], guide_hint NHWC [B,h,w,M]) (compression.py:215-273).
+
+        isolate=True returns (c_latent, guide_hint, errors): a stream fails on its own and the batch goes on.
+        errors[b] is None, or the exception image b would have raised alone: a z string that does not decode, or a
+        rANS status other than 0 in any of the 20 stages. strings_list[b] may itself be an exception (a body that
+        did not parse): it is carried into errors[b]. An image that fails before the device work runs with zero z
+        indexes and no decoder; one that fails in a stage decodes zeros from there on. The launches are the ones of
+        isolate=False (one recorded plan serves both), the survivors' rows are what they decode to alone, and the
+        failed rows are returned as zeros."""
+        self.update()
+        B = len(strings_list)
+        hz, wz = self.check_z_shape(shape)
+        errors: List[Optional[Exception]] = [None] * B
+        if not isolate:
+            zi = np.stack([coders.ac_decode_uniform(st[1][0], hz * wz, self.codebook_size) for st in strings_list])
+        else:
+            zi = np.zeros((B, hz * wz), dtype=np.int16)
+            for b, st in enumerate(strings_list):
+                try:
+                    if isinstance(st, Exception):
+                        raise st
+                    zi[b] = coders.ac_decode_uniform(st[1][0], hz * wz, self.codebook_size)
+                    st[0][0]  # a header that announces fewer strings than two
+                except Exception as e:  # noqa: BLE001 — the reference's convention: any exception is a decode failure
+                    errors[b] = e
         self.last_z_idx = zi  # [B, hz * wz] VQ indices of this call (the validation epoch's codebook usage)
         z_idx = torch.from_numpy(zi.astype(np.int32).reshape(B, hz, wz)).to(device)
 
-        def fresh_decoders():  # the decoders are stateful: one fresh set per execution of the region
+        def close_decoders():
             for d in self._io.get("decs", []):
-                d.close()
-            self._io["decs"] = [coders.RansDecoder(st[0][0]) for st in strings_list]
+                if d is not None:
+                    d.close()
+
+        def fresh_decoders():  # the decoders are stateful: one fresh set per execution of the region
+            close_decoders()
+            self._io["decs"] = [None if errors[b] is not None else coders.RansDecoder(st[0][0])
+                                for b, st in enumerate(strings_list)]
+            if isolate:
+                self._io["status"] = np.zeros(B, dtype=np.int32)
 
         self._io = {}
         try:
             c_latent, guide_hint = self._run_region("decompress", self._decompress_gpu, [z_idx], before=fresh_decoders)
             if self.use_plans:  # the plan's outputs are its static buffers
                 c_latent, guide_hint = c_latent.clone(), guide_hint.clone()
+            status = self._io.get("status")
         finally:
-            for d in self._io.get("decs", []):
-                d.close()
+            close_decoders()
             self._io = {}
-        return c_latent, guide_hint
+        if not isolate:
+            return c_latent, guide_hint
+        for b in range(B):
+            if errors[b] is None and status[b] != 0:
+                errors[b] = (_lib.BitstreamError if status[b] == _lib.EBADMSG else _lib.RdeicError)(
+                    "rdeic_rans_decode_batch", int(status[b]))
+        bad = [b for b in range(B) if errors[b] is not None]
+        if bad:
+            c_latent[bad] = 0
+            guide_hint[bad] = 0
+        return c_latent, guide_hint, errors

@@ -464,7 +464,7 @@ extern "C" {
 int rdeic_version(void) { return 1; }
 
 // number of entry points declared in include/rdeic_hip.h (checked by tests/test_abi.py)
-int rdeic_abi_count(void) { return 124; }
+int rdeic_abi_count(void) { return 125; }
 
 static int pmf_to_quantized_cdf_impl(const float* pmf, int32_t n, int32_t precision, uint32_t* cdf_out) {
   if (!pmf || !cdf_out || n <= 0 || precision <= 0 || precision > 24) return RDEIC_EINVAL;
@@ -669,6 +669,33 @@ int rdeic_rans_decode_batch(int32_t count, void** handles, const int32_t* idx, s
     });
     for (int v : rc)
       if (v) return v;
+    return (int)RDEIC_OK;
+  });
+}
+
+// Fault-isolating form: one stream's failure is that stream's status, never the call's. A stream
+// whose status is already nonzero (it failed in an earlier stage) or whose handle is null is not
+// touched. Every skipped or failed stream's n_per symbols are written as 0, so a consumer of the
+// whole `out` buffer (rdeic_ckbd_dequant reads it from pinned memory) never sees stale values.
+int rdeic_rans_decode_batch_status(int32_t count, void** handles, const int32_t* idx, size_t n_per, size_t stride,
+                                   const int32_t* cdf, int32_t cdf_ld, const int32_t* cdf_len, const int32_t* offset,
+                                   int32_t levels, int32_t* out, int32_t threads, int32_t* status) {
+  if (count <= 0 || !handles || !idx || !out || !status || !cdf || !cdf_len || !offset || stride < n_per)
+    return RDEIC_EINVAL;
+  return guard([&] {
+    parallel_for(count, threads, [&](int32_t i) {
+      int32_t* o = out + (size_t)i * stride;
+      int rc = status[i];
+      const bool run = handles[i] && rc == 0;
+      if (run) {
+        rc = guard([&] {
+          return rans_decode_impl((RansDecoder*)handles[i], idx + (size_t)i * stride, n_per, cdf, cdf_ld, cdf_len,
+                                  offset, levels, o);
+        });
+        status[i] = rc;
+      }
+      if (!run || rc != RDEIC_OK) std::fill(o, o + n_per, 0);
+    });
     return (int)RDEIC_OK;
   });
 }

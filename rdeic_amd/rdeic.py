@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import os
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -272,12 +272,39 @@ class RDEIC:
         return [bitstream.pack_body(o["shape"], o["strings"]) for o in outs]
 
     @torch.no_grad()
-    def decompress_bodies(self, bodies: Sequence[bytes]):
-        parsed = [bitstream.unpack_body(b) for b in bodies]
-        shape = parsed[0][1]
-        if any(p[1] != shape for p in parsed):
-            raise ValueError("batched decompress needs one latent shape per batch")
-        return self.preprocess_model.decompress([p[0] for p in parsed], shape, device=self.device)
+    def decompress_bodies(self, bodies: Sequence[bytes], isolate: bool = False,
+                          expect_shape: Optional[Tuple[int, int]] = None):
+        """Bodies of one latent shape -> (c_latent, guide_hint). isolate=True returns (c_latent, guide_hint, errors)
+        instead of raising for one bad body: errors[b] is None or the exception body b raises alone — its header or
+        strings do not parse, its latent shape is implausible or not the batch's, its z string does not decode, or its
+        rANS stream fails in any stage (Compression.decompress). The batch's shape is expect_shape; without it, the
+        first parseable body's plausible shape. For hostile input pass expect_shape: a flipped header can announce
+        another plausible shape, and if that body comes first the good bodies are the mismatches. Rows of failed
+        bodies are zeros and must not be used; when no body reaches the device both tensors are None."""
+        if not isolate:
+            parsed = [bitstream.unpack_body(b) for b in bodies]
+            shape = parsed[0][1]
+            if any(p[1] != shape for p in parsed):
+                raise ValueError("batched decompress needs one latent shape per batch")
+            return self.preprocess_model.decompress([p[0] for p in parsed], shape, device=self.device)
+        parsed = []
+        for b in bodies:
+            try:
+                p = bitstream.unpack_body(b)
+                Compression.check_z_shape(p[1])  # an implausible shape is that body's own failure, first body or not
+                parsed.append(p)
+            except Exception as e:  # noqa: BLE001 — the reference's convention: any exception is a decode failure
+                parsed.append(e)
+        shape = tuple(expect_shape) if expect_shape is not None else \
+            next((tuple(p[1]) for p in parsed if not isinstance(p, Exception)), None)
+        strings = []
+        for p in parsed:
+            if not isinstance(p, Exception) and tuple(p[1]) != shape:
+                p = ValueError(f"corrupted header: latent shape {tuple(p[1])} != {shape}")
+            strings.append(p if isinstance(p, Exception) else p[0])
+        if all(isinstance(s, Exception) for s in strings):
+            return None, None, strings
+        return self.preprocess_model.decompress(strings, shape, device=self.device, isolate=True)
 
     @staticmethod
     def _sampler(model, sampler: str):

@@ -10,6 +10,12 @@ relay-denoise + VAE-decode launch.
 Latent corruption draws its randoms from a CPU generator seeded like the reference's
 torch.manual_seed(seed) (identical to the reference on CPU tensors; the reference's CUDA-RNG draws
 cannot be reproduced on another device, so on-device inputs are corrupted through the CPU copy).
+
+run_robustness is the batched form of the sweep: the variants of an image are entropy-decoded
+together with per-stream fault isolation (decode_isolated), the latent error space is covered, and
+summary_by_rate / failure_thresholds restate the reference's tables. For the bitstream space it returns the
+records run_bitstream_robustness returns, for images of at least 176 pixels a side whose sides are multiples of 16
+(elsewhere the two differ in what they put where SSIM / MS-SSIM does not apply: see run_robustness).
 """
 from __future__ import annotations
 
@@ -225,3 +231,289 @@ def write_csv(records: Sequence[Dict], path: str) -> None:
         w.writeheader()
         for r in records:
             w.writerow(r)
+
+
+# ------------------------------------------------------------------ batched sweep (run_robustness.py:188-370)
+BITSTREAM_TYPES = ("random", "burst")
+LATENT_TYPES = ("mask_replace", "additive")
+COLUMNS = ["image_id", "error_space", "error_type", "error_rate", "seed", "bpp", "psnr", "ssim", "ms_ssim", "lpips",
+           "decode_failed"]
+SUMMARY_METRICS = ("psnr", "ssim", "ms_ssim", "lpips")
+# plot_robustness.py:136-143: the value a rate's mean has to cross, and on which side failure lies
+THRESHOLDS = {"psnr": 25.0, "ssim": 0.85, "ms_ssim": 0.9, "lpips": 0.3}
+HIGHER_BETTER = {"psnr": True, "ssim": True, "ms_ssim": True, "lpips": False}
+NAN = float("nan")
+
+
+def check_error_pair(error_space: str, error_type: str) -> None:
+    """bitstream takes random | burst, latent takes mask_replace | additive (Corruptor's own rule)."""
+    allowed = {"bitstream": BITSTREAM_TYPES, "latent": LATENT_TYPES}.get(error_space)
+    if allowed is None:
+        raise ValueError(f"error_space {error_space!r} (bitstream | latent)")
+    if error_type not in allowed:
+        raise ValueError(f"error_type {error_type!r} does not go with error_space {error_space!r} "
+                         f"({' | '.join(allowed)})")
+
+
+def corrupt_latent_nhwc(c_latent: torch.Tensor, mode: str, rate: float, seed: int = 42,
+                        valid_range: Tuple[float, float] = (-3.0, 3.0)) -> torch.Tensor:
+    """latent_corrupt on the project's NHWC latent [B,h,w,4], in the reference's NCHW element order: the CPU
+    generator's k-th draw lands on the element it lands on in the reference's [B,4,h,w] tensor."""
+    x = c_latent.permute(0, 3, 1, 2).contiguous()
+    return latent_corrupt(x, mode, rate, seed, valid_range).permute(0, 2, 3, 1).contiguous()
+
+
+def decode_isolated(model, bodies: Sequence[bytes], expect_shape: Tuple[int, int], batch_size: int = 8) -> List:
+    """Entropy-decode many bodies of one latent shape in chunks of exactly `batch_size` (the launch plans key on the
+    batch size: the tail chunk is padded by repeating its last body, and the padding rows are dropped). One entry
+    per body: (c_latent [1,h,w,4], guide_hint [1,h,w,M]) or the exception that body raises alone."""
+    out: List = []
+    bs = max(1, int(batch_size))
+    for s in range(0, len(bodies), bs):
+        chunk = list(bodies[s:s + bs])
+        real = len(chunk)
+        chunk += [chunk[-1]] * (bs - real)
+        lat, hint, errors = model.decompress_bodies(chunk, isolate=True, expect_shape=expect_shape)
+        for k in range(real):
+            out.append(errors[k] if errors[k] is not None else (lat[k:k + 1], hint[k:k + 1]))
+    return out
+
+
+def relay_decode_chunked(model, lat: Sequence[torch.Tensor], hint: Sequence[torch.Tensor], context: torch.Tensor,
+                         noise_nchw: torch.Tensor, step_noise_nchw: Optional[torch.Tensor], steps: int, sampler: str,
+                         batch_size: int = 8) -> torch.Tensor:
+    """relay_decode_u8 of n single-row latents / hints in chunks of `batch_size`. The tail chunk is padded, by
+    repeating its last row, to the next multiple of a quarter chunk: the relay is compute-bound per row (a padded row
+    costs what a real one does, unlike in the entropy decode), so the padding is bounded to batch_size / 4 - 1 rows
+    and the recorded plans to four batch sizes, whatever the survivor counts of a sweep are.
+    noise_nchw [n,4,h,w] and step_noise_nchw [steps,n,4,h,w] are CPU tensors. -> uint8 [n,H,W,3]."""
+    n, bs = len(lat), max(1, int(batch_size))
+    granule = max(1, bs // 4)
+    dev = lat[0].device
+    outs = []
+    for s in range(0, n, bs):
+        idx = list(range(s, min(n, s + bs)))
+        real = len(idx)
+        idx += [idx[-1]] * (-(-real // granule) * granule - real)
+        noise = ops.nchw_to_nhwc(noise_nchw[idx].to(dev), torch.float32)
+        step = None
+        if sampler == "ddpm":
+            step = torch.stack([ops.nchw_to_nhwc(step_noise_nchw[t][idx].to(dev), torch.float32)
+                                for t in range(steps)])
+        out = model.relay_decode_u8(torch.cat([lat[k] for k in idx]), torch.cat([hint[k] for k in idx]), context,
+                                    noise, steps, sampler, step)
+        outs.append(out[:real])
+    return torch.cat(outs)
+
+
+def score_crop(pred: torch.Tensor, target: torch.Tensor, lpips=None, dists=None, pred_np: Optional[np.ndarray] = None,
+               target_np: Optional[np.ndarray] = None) -> Dict:
+    """The metric columns of one cropped reconstruction, uint8 [1,h,w,3] device tensors. PSNR as psnr_u8 has it
+    (pred_np / target_np [h,w,3]: host copies the caller already holds); the device metrics by ood.score_image's
+    rules (NaN where the crop's size rules a metric out). Without an LPIPS model lpips stays None, as in
+    run_bitstream_robustness."""
+    from . import metrics
+    h, w = pred.shape[1:3]
+    out = {"psnr": psnr_u8(pred[0].cpu().numpy() if pred_np is None else pred_np,
+                           target[0].cpu().numpy() if target_np is None else target_np),
+           "ssim": NAN, "ms_ssim": NAN, "lpips": None}
+    if min(h, w) >= 176 and h % 16 == 0 and w % 16 == 0:
+        s, ms = metrics.ssim_ms_ssim(pred, target)
+        out.update(ssim=float(s[0]), ms_ssim=float(ms[0]))
+    elif min(h, w) >= 176:
+        out.update(ssim=float(metrics.ssim_levels(pred, target, 1)[0, 0, 0]))
+    if lpips is not None:
+        from .lpips import MIN_SIZE
+        out["lpips"] = float(lpips(pred, target)[0]) if min(h, w) >= MIN_SIZE[lpips.net] else NAN
+    if dists is not None:
+        out["dists"] = float(dists(pred, target)[0])
+    return out
+
+
+@torch.no_grad()
+def run_robustness(model, images: torch.Tensor, context: torch.Tensor, error_space: str, error_type: str,
+                   rates: Sequence[float], seeds: Sequence[int], steps: int = 2, sampler: str = "ddpm",
+                   noise_seed: int = 231, image_ids: Optional[Sequence[str]] = None, mean_burst_len: float = 8.0,
+                   batch_size: int = 8, lpips=None, dists=None, orig_sizes: Optional[Sequence[Tuple[int, int]]] = None,
+                   recon_cb=None, bodies: Optional[Sequence[bytes]] = None) -> List[Dict]:
+    """The reference's sweep (run_robustness.py:227-350) over uint8 images [B,H,W,3] already padded to multiples of
+    64: one record per (image, rate, seed), rates as fractions, in that loop order, with the reference's columns
+    (`dists` too with a DISTS model, `error` on a failure row).
+
+    bitstream (random | burst): every image is encoded once (or its stream is given in `bodies`), corrupted per
+    (rate, seed), and all variants are entropy-decoded in chunks of `batch_size` with per-stream fault isolation
+    (decode_isolated): a variant that fails is the reference's failure row (psnr 0, ssim 0, ms_ssim 0, lpips 1).
+    latent (mask_replace | additive): the clean stream is decoded once, c_latent is corrupted per (rate, seed) in
+    the reference's NCHW order with valid_range (-3, 3), guide_hint is reused unchanged; no row can fail.
+    The survivors are relay-decoded in job order in chunks of `batch_size` (relay_decode_chunked). The noise rule is
+    run_bitstream_robustness's — one CPU generator seeded noise_seed, randn([n,4,h,w]) for the n survivors, then one
+    such draw per ddpm step — so for the bitstream space the two functions return the same records where H, W >= 176
+    and both are multiples of 16 (and no orig_sizes crop is asked for). Elsewhere only the SSIM columns differ: under
+    176 pixels the old function leaves ssim / ms_ssim None and this one writes NaN, and at 176 and more but no
+    multiple of 16 the old one calls ssim_ms_ssim on the whole batch where this one scores SSIM alone (ms_ssim NaN).
+    Scores are taken on the crop [:h,:w] of orig_sizes[i] = (h, w) against the cropped original (:311-314).
+    recon_cb(record, crop uint8 [h,w,3] numpy) is called for every decoded row."""
+    check_error_pair(error_space, error_type)
+    B, H, W, _ = images.shape
+    ids = list(image_ids) if image_ids is not None else [f"img{i}" for i in range(B)]
+    sizes = [tuple(s) for s in orig_sizes] if orig_sizes is not None else [(H, W)] * B
+    if bodies is None:
+        bodies = model.compress_images(images)
+    shape0 = bitstream.unpack_body(bodies[0])[1]
+    jobs: List[Tuple[int, Dict]] = []
+    payload: List = []
+    if error_space == "bitstream":
+        variants = [Corruptor("bitstream", error_type, rate, seed, mean_burst_len).corrupt_bytes(bodies[i])
+                    for i in range(B) for rate in rates for seed in seeds]
+        payload = decode_isolated(model, variants, shape0, batch_size)
+    else:
+        for i in range(B):
+            c_lat, hint = model.decompress_bodies([bodies[i]])
+            payload += [(corrupt_latent_nhwc(c_lat, error_type, rate, seed), hint) for rate in rates for seed in seeds]
+    k = 0
+    for i in range(B):
+        bpp = 8.0 * len(bodies[i]) / (H * W)  # 8 * filesize / (padded H * W) (run_robustness.py:250-251)
+        for rate in rates:
+            for seed in seeds:
+                r = payload[k]
+                k += 1
+                rec = {"image_id": ids[i], "error_space": error_space, "error_type": error_type,
+                       "error_rate": rate * 100, "seed": seed, "bpp": bpp, "psnr": 0.0, "ssim": None, "ms_ssim": None,
+                       "lpips": None, "decode_failed": isinstance(r, Exception)}
+                if dists is not None:
+                    rec["dists"] = None
+                if rec["decode_failed"]:  # the reference's failure row (run_robustness.py:280-295)
+                    rec.update(ssim=0.0, ms_ssim=0.0, lpips=1.0, error=f"{type(r).__name__}: {r}")
+                    if dists is not None:
+                        rec["dists"] = 1.0
+                jobs.append((i, rec))
+    ok = [j for j in range(len(jobs)) if not jobs[j][1]["decode_failed"]]
+    if ok:
+        n = len(ok)
+        h, w = payload[ok[0]][0].shape[1:3]
+        gen = torch.Generator().manual_seed(noise_seed)
+        noise = torch.randn((n, 4, h, w), generator=gen)
+        step_noise = None
+        if sampler == "ddpm":
+            step_noise = torch.stack([torch.randn((n, 4, h, w), generator=gen) for _ in range(steps)])
+        out_d = relay_decode_chunked(model, [payload[j][0] for j in ok], [payload[j][1] for j in ok], context, noise,
+                                     step_noise, steps, sampler, batch_size)
+        tgt = images.to(out_d.device)
+        out, ref = out_d.cpu().numpy(), images.cpu().numpy()
+        for m, j in enumerate(ok):
+            i, rec = jobs[j]
+            ch, cw = sizes[i]
+            pred = out_d[m:m + 1, :ch, :cw, :].contiguous()
+            rec.update(score_crop(pred, tgt[i:i + 1, :ch, :cw, :].contiguous(), lpips, dists, out[m, :ch, :cw],
+                                  ref[i, :ch, :cw]))
+            if recon_cb is not None:
+                recon_cb(rec, np.ascontiguousarray(out[m, :ch, :cw]))
+    return [rec for _, rec in jobs]
+
+
+def write_records_csv(records: Sequence[Dict], path: str, columns: Optional[Sequence[str]] = None) -> None:
+    """The results table of a sweep: COLUMNS (`dists` after `lpips` when the records carry it) or the given
+    columns; a value that was not scored (None) is written as nan."""
+    import csv
+    cols = list(columns) if columns is not None else list(COLUMNS)
+    if "dists" not in cols and any("dists" in r for r in records):
+        cols.insert(cols.index("lpips") + 1, "dists")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=cols, restval=NAN, extrasaction="ignore")
+        w.writeheader()
+        for r in records:
+            w.writerow({k: (NAN if v is None else v) for k, v in r.items()})
+
+
+def read_csv(path: str) -> List[Dict]:
+    """A results CSV (write_csv's, the reference's, or the JPEG2000 table) back into records: numbers as floats,
+    seed as int, decode_failed as bool, empty cells as NaN."""
+    import csv
+    out = []
+    with open(path, newline="") as f:
+        for row in csv.DictReader(f):
+            rec: Dict = {}
+            for key, v in row.items():
+                if key in ("image_id", "error_space", "error_type", "codec"):
+                    rec[key] = v
+                elif key == "decode_failed":
+                    rec[key] = v.strip().lower() in ("true", "1")
+                elif key == "seed":
+                    rec[key] = int(v)
+                else:
+                    rec[key] = float(v) if v.strip() else NAN
+            out.append(rec)
+    return out
+
+
+def _by_rate(records: Sequence[Dict], key: str) -> Dict[float, np.ndarray]:
+    """{error rate: the finite-or-inf values of `key` at that rate (None and NaN dropped)}, rates ascending."""
+    rates = sorted({float(r["error_rate"]) for r in records})
+    out = {}
+    for rate in rates:
+        v = np.array([NAN if r.get(key) is None else float(r[key]) for r in records
+                      if float(r["error_rate"]) == rate], dtype=np.float64)
+        out[rate] = v[~np.isnan(v)]
+    return out
+
+
+def summary_by_rate(records: Sequence[Dict]) -> List[Dict]:
+    """The reference's printed table (run_robustness.py:362-370, a groupby on error_rate): per error rate, ascending,
+    {"error_rate", "<metric>": (mean, sample std with ddof 1) for psnr / ssim / ms_ssim / lpips, "decode_failed":
+    count}. NaN (and None) values are skipped, as pandas does; a mean of nothing and a std of fewer than two are NaN."""
+    cols = {m: _by_rate(records, m) for m in SUMMARY_METRICS}
+    out = []
+    for rate in sorted({float(r["error_rate"]) for r in records}):
+        row: Dict = {"error_rate": rate}
+        for m in SUMMARY_METRICS:
+            v = cols[m][rate]
+            row[m] = (float(v.mean()) if v.size else NAN, float(v.std(ddof=1)) if v.size > 1 else NAN)
+        row["decode_failed"] = sum(1 for r in records if float(r["error_rate"]) == rate and r["decode_failed"])
+        out.append(row)
+    return out
+
+
+def format_summary(records: Sequence[Dict]) -> str:
+    """summary_by_rate as text, values rounded to 4 places like the reference's `.round(4)`."""
+    lines = ["error_rate  " + "  ".join(f"{m + ' mean':>13} {m + ' std':>11}" for m in SUMMARY_METRICS)
+             + "  decode_failed"]
+    for row in summary_by_rate(records):
+        lines.append(f"{row['error_rate']:>10g}  " + "  ".join(f"{row[m][0]:>13.4f} {row[m][1]:>11.4f}"
+                                                              for m in SUMMARY_METRICS)
+                     + f"  {row['decode_failed']:>13d}")
+    return "\n".join(lines)
+
+
+def failure_thresholds(records: Sequence[Dict]) -> List[Dict]:
+    """plot_robustness.compute_failure_thresholds (:130-175): per metric, the first error rate (ascending) whose mean
+    over all rows (NaN skipped) is below the threshold — above it for lpips; where no rate crosses, ">10%" with the
+    last rate's mean. One row per metric: metric, threshold, failure_rate, metric_at_failure."""
+    out = []
+    for m, thr in THRESHOLDS.items():
+        means = [(rate, float(v.mean()) if v.size else NAN) for rate, v in _by_rate(records, m).items()]
+        hit = next(((rate, mean) for rate, mean in means if (mean < thr if HIGHER_BETTER[m] else mean > thr)), None)
+        rate, mean = hit if hit is not None else (">10%", means[-1][1])
+        out.append({"metric": m, "threshold": thr, "failure_rate": rate, "metric_at_failure": mean})
+    return out
+
+
+def write_failure_thresholds(records: Sequence[Dict], output_dir: str, prefix: str = "") -> List[Dict]:
+    """<prefix>failure_thresholds.csv and .txt as the reference writes them (plot_robustness.py:177-193)."""
+    import csv
+    rows = failure_thresholds(records)
+    os.makedirs(output_dir, exist_ok=True)
+    with open(os.path.join(output_dir, f"{prefix}failure_thresholds.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["metric", "threshold", "failure_rate", "metric_at_failure"])
+        w.writeheader()
+        for r in rows:
+            w.writerow(r)
+    with open(os.path.join(output_dir, f"{prefix}failure_thresholds.txt"), "w") as f:
+        f.write("RDEIC Robustness Failure Thresholds\n")
+        f.write("=" * 50 + "\n\n")
+        for r in rows:
+            f.write(f"{r['metric'].upper()}:\n")
+            f.write(f"  Threshold: {r['threshold']}\n")
+            f.write(f"  Failure at: {r['failure_rate']}% error rate\n")
+            f.write(f"  Value at failure: {r['metric_at_failure']:.4f}\n\n")
+    return rows
