@@ -475,6 +475,34 @@ int rdeic_dists_moments(const float* x, int32_t ldx, const float* y, int32_t ldy
  * alpha, beta: c device doubles, already normalised by the sum over all taps. */
 int rdeic_dists_score(const double* mom, const double* alpha, const double* beta, int32_t n, int32_t c,
                       int32_t accumulate, double* out, void* stream);
+/* The DISTS training loss (rdeic_amd/dists.py DISTS.loss) and its backward, prediction side only. No atomics:
+ * every output element is one fixed-order sum.
+ * prep of float images in [-1, 1]: img NHWC fp32 (dtype 0) / bf16 (1) with pixel stride ld >= 3 -> raw and norm,
+ * both fp32 [npix][4] (16-byte aligned): r = v * 0.5f + 0.5f (a multiply, then an add), norm = (r - mean_c) / std_c
+ * in that order in fp32; channel 3 of both is zero. */
+int rdeic_dists_prep_float(const void* img, int32_t ld, int32_t dtype, int64_t npix, float* raw, float* norm,
+                           void* stream);
+/* dpred [npix] pixels of stride ld_dpred, fp32 (dtype 0) / bf16 (1), channel c < 3 =
+ * 0.5f * (dnorm_c / std_c + draw_c): dnorm, draw fp32 4-channel gradients of the two prep outputs (strides % 4 == 0,
+ * 16-byte aligned). */
+int rdeic_dists_prep_bwd(const float* dnorm, int32_t ld_dnorm, const float* draw, int32_t ld_draw, int64_t npix,
+                         void* dpred, int32_t ld_dpred, int32_t dtype, void* stream);
+/* input gradient of rdeic_dists_l2pool in gather form: dx_j = x_j * sum_o g_(o,j) dy_o / y_o over the (at most
+ * 2 x 2) windows o that hold j, in output row-major order. x [n][h][w][c] the pool's input, y its stored output,
+ * dy the output's gradient (both [n][ceil(h/2)][ceil(w/2)][c]); x_j == 0 gives exactly 0. */
+int rdeic_dists_l2pool_bwd(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ld_x, const float* y,
+                           int32_t ld_y, const float* dy, int32_t ld_dy, float* dx, int32_t ld_dx, void* stream);
+/* The backward of rdeic_dists_score through rdeic_dists_moments, in two launches. score_bwd: from the moments
+ * [n][5][c] and gs[n] (device doubles, the upstream gradient of each image's score) the fp64 coefficients
+ * coef [n][5][c] of d/dx_p = A + B (y_p - my) + C (x_p - mx): A = g alpha (2 my - 2 mx S1) / (den1 hw),
+ * B = 2 g beta / (den2 hw), C = -B S2, den1 = mx^2 + my^2 + 1e-6, den2 = vx + vy + 1e-6. Stored are
+ * A + B (ky - my) + C (kx - mx), B, C, kx, ky with kx, ky the fp32 roundings of the means (the metric's shifts). */
+int rdeic_dists_score_bwd(const double* mom, const double* alpha, const double* beta, const double* gs, int32_t n,
+                          int64_t hw, int32_t c, double* coef, void* stream);
+/* tap_bwd: dx [n][hw][c] (pixel stride ld_dx; += when accumulate) = A' + B (y - ky) + C (x - kx), the differences
+ * in fp32, the rest in fp64, rounded once. Two identical maps give exactly 0. */
+int rdeic_dists_tap_bwd(const float* x, int32_t ldx, const float* y, int32_t ldy, const double* coef, int32_t n,
+                        int64_t hw, int32_t c, int32_t accumulate, float* dx, int32_t ld_dx, void* stream);
 
 /* ------------------------------------------------------------ FID / KID (fid.hip)
  * The kernels around the fp32 InceptionV3 convs of the FID / KID feature tower (layer table, weights, chunking and

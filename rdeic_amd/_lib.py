@@ -162,6 +162,11 @@ PROTOTYPES = {
     "rdeic_dists_moments_ws_doubles": (_sz, [_i32, _i64, _i32]),
     "rdeic_dists_moments": (C.c_int, [_p, _i32, _p, _i32, _i32, _i64, _i32, _p, _sz, _p, _p]),
     "rdeic_dists_score": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p]),
+    "rdeic_dists_prep_float": (C.c_int, [_p, _i32, _i32, _i64, _p, _p, _p]),
+    "rdeic_dists_prep_bwd": (C.c_int, [_p, _i32, _p, _i32, _i64, _p, _i32, _i32, _p]),
+    "rdeic_dists_l2pool_bwd": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _p]),
+    "rdeic_dists_score_bwd": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _p, _p]),
+    "rdeic_dists_tap_bwd": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i64, _i32, _i32, _p, _i32, _p]),
     # FID / KID (fid.hip)
     "rdeic_fid_prep": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "rdeic_pool2d": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p]),

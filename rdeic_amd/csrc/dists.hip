@@ -351,7 +351,262 @@ void launch_moments(bool wide, dim3 grid, hipStream_t s, const float* x, int ldx
                        part);
 }
 
+// ---------------------------------------------------------------- the training loss (DISTS.loss) and its backward
+// prep of float images in [-1, 1]: r = v * 0.5f + 0.5f (a multiply, then an add), norm = (r - mean_c) / std_c
+template <typename T>
+__global__ __launch_bounds__(256) void dists_prep_float_kernel(const T* __restrict__ img, int ld, long npix,
+                                                               Affine3 af, float* __restrict__ raw,
+                                                               float* __restrict__ norm) {
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
+    const T* s = img + p * ld;
+    f32x4 r, v;
+    r.x = to_f32(s[0]) * 0.5f + 0.5f;
+    r.y = to_f32(s[1]) * 0.5f + 0.5f;
+    r.z = to_f32(s[2]) * 0.5f + 0.5f;
+    r.w = 0.f;
+    v.x = (r.x - af.mean[0]) / af.std[0];
+    v.y = (r.y - af.mean[1]) / af.std[1];
+    v.z = (r.z - af.mean[2]) / af.std[2];
+    v.w = 0.f;
+    *reinterpret_cast<f32x4*>(raw + p * 4) = r;
+    *reinterpret_cast<f32x4*>(norm + p * 4) = v;
+  }
+}
+
+// dpred_c = 0.5f * (dnorm_c / std_c + draw_c): the two gradients that reach the image, in the caller's dtype
+template <typename T>
+__global__ __launch_bounds__(256) void dists_prep_bwd_kernel(const float* __restrict__ dnorm, int ldn,
+                                                             const float* __restrict__ draw, int ldr, long npix,
+                                                             Affine3 af, T* __restrict__ dpred, int ldp) {
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(dnorm + p * ldn);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(draw + p * ldr);
+    T* o = dpred + p * ldp;
+    o[0] = from_f32<T>(0.5f * (a.x / af.std[0] + b.x));
+    o[1] = from_f32<T>(0.5f * (a.y / af.std[1] + b.y));
+    o[2] = from_f32<T>(0.5f * (a.z / af.std[2] + b.z));
+  }
+}
+
+// The L2 pool's input gradient in gather form: one thread per V channels of one input pixel. Input row iy lies in
+// the windows oy with 2 oy - 1 + d == iy: one (d = 1) for an even row, two (d = 2 at oy = (iy - 1) / 2, then d = 0
+// at oy = (iy + 1) / 2) for an odd one, columns likewise, visited in output row-major order; a window outside
+// the output is skipped. y is the stored forward output (>= 1e-6), so x == 0 gives exactly 0.
+template <int V>
+__global__ __launch_bounds__(256) void l2pool_bwd_kernel(const float* __restrict__ x, int h, int w, int c, int ldx,
+                                                         const float* __restrict__ y, int ldy,
+                                                         const float* __restrict__ dy, int lddy, int ho, int wo,
+                                                         float* __restrict__ dx, int lddx, long total) {
+  const int cv = c / V;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int ch = (int)(i % cv) * V;
+    const long ip = i / cv;  // input pixel over the batch
+    const int ix = (int)(ip % w);
+    const long t = ip / w;
+    const int iy = (int)(t % h);
+    const long img = t / h;
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    const int ny = (iy & 1) ? 2 : 1, nx = (ix & 1) ? 2 : 1;
+    for (int a = 0; a < ny; ++a) {
+      const int oy = (iy & 1) ? (iy - 1) / 2 + a : iy / 2;
+      if (oy >= ho) continue;
+      for (int b = 0; b < nx; ++b) {
+        const int ox = (ix & 1) ? (ix - 1) / 2 + b : ix / 2;
+        if (ox >= wo) continue;
+        const float g = ((iy & 1) ? 1.f : 2.f) * ((ix & 1) ? 1.f : 2.f) * 0.0625f;
+        const long op = (img * ho + oy) * wo + ox;
+        const float* qy = y + op * ldy + ch;
+        const float* qd = dy + op * lddy + ch;
+        if constexpr (V == 4) {
+          const f32x4 yv = *reinterpret_cast<const f32x4*>(qy);
+          const f32x4 dv = *reinterpret_cast<const f32x4*>(qd);
+          acc[0] += g * (dv.x / yv.x); acc[1] += g * (dv.y / yv.y);
+          acc[2] += g * (dv.z / yv.z); acc[3] += g * (dv.w / yv.w);
+        } else {
+          acc[0] += g * (qd[0] / qy[0]);
+        }
+      }
+    }
+    const float* qx = x + ip * ldx + ch;
+    float* o = dx + ip * lddx + ch;
+    if constexpr (V == 4) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(qx);
+      *reinterpret_cast<f32x4*>(o) = f32x4{xv.x * acc[0], xv.y * acc[1], xv.z * acc[2], xv.w * acc[3]};
+    } else {
+      o[0] = qx[0] * acc[0];
+    }
+  }
+}
+
+// The tap score's backward, part 1: one thread per (image, channel), fp64. With g = gs[img] (the upstream gradient
+// of the image's score), S1, S2 as in the score kernel, den1 = mx^2 + my^2 + c1, den2 = vx + vy + c2:
+//   d / d x_p = A + B (y_p - my) + C (x_p - mx),
+//   A = g alpha (2 my - 2 mx S1) / (den1 hw),  B = 2 g beta / (den2 hw),  C = -B S2.
+// The apply kernel subtracts the metric's fp32 shifts kx = (float)mx, ky = (float)my, so what is stored is
+// coef[img][5][c] = A + B (ky - my) + C (kx - mx), B, C, kx, ky. Two identical maps give S1 == S2 == 1 exactly,
+// so A == 0 and C == -B, and with contraction off the two shift products cancel exactly.
+__global__ __launch_bounds__(256) void dists_score_bwd_kernel(const double* __restrict__ mom,
+                                                              const double* __restrict__ alpha,
+                                                              const double* __restrict__ beta,
+                                                              const double* __restrict__ gs, int c, double hw,
+                                                              double* __restrict__ coef) {
+  const long img = blockIdx.y;
+  const int ch = blockIdx.x * 256 + threadIdx.x;
+  if (ch >= c) return;
+  const double* m = mom + img * 5 * c;
+  const double c1 = 1e-6, c2 = 1e-6, g = gs[img];
+  const double mx = m[ch], my = m[c + ch], vx = m[2L * c + ch], vy = m[3L * c + ch], cxy = m[4L * c + ch];
+  const double den1 = (mx * mx + my * my) + c1, den2 = (vx + vy) + c2;
+  const double s1 = (2.0 * (mx * my) + c1) / den1;
+  const double s2 = (2.0 * cxy + c2) / den2;
+  const double A = g * alpha[ch] * (2.0 * my - 2.0 * mx * s1) / (den1 * hw);
+  const double B = 2.0 * g * beta[ch] / (den2 * hw);
+  const double C = -B * s2;
+  const double kx = (double)(float)mx, ky = (double)(float)my;
+  double* o = coef + img * 5 * c + ch;
+  o[0] = (A + B * (ky - my)) + C * (kx - mx);
+  o[c] = B;
+  o[2L * c] = C;
+  o[3L * c] = kx;
+  o[4L * c] = ky;
+}
+
+// Part 2, element-wise: grid (pixel chunks, channel blocks, n) with the moment passes' thread mapping (tx channel
+// groups of 4 by ty pixel rows). A thread holds its channels' coefficients and walks TAPB_RUN pixels;
+// dx (+)= (float)((A + B (double)(y - ky)) + C (double)(x - kx)), the differences in fp32 as the metric takes them.
+constexpr int TAPB_RUN = 8;
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void dists_tap_bwd_kernel(const float* __restrict__ x, int ldx,
+                                                            const float* __restrict__ y, int ldy,
+                                                            const double* __restrict__ coef, long hw, int c, int tx,
+                                                            int accumulate, float* __restrict__ dx, int ldd) {
+  const int ty = 256 / tx;
+  const int cx = threadIdx.x & (tx - 1), py = threadIdx.x / tx;
+  const long img = blockIdx.z;
+  const int ch = (blockIdx.y * tx + cx) * 4;
+  if (ch >= c) return;
+  const double* cf = coef + img * 5 * c;
+  double A[4], B[4], C[4];
+  float kx[4], ky[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const bool in = ch + e < c;
+    A[e] = in ? cf[ch + e] : 0.0;
+    B[e] = in ? cf[c + ch + e] : 0.0;
+    C[e] = in ? cf[2L * c + ch + e] : 0.0;
+    kx[e] = in ? (float)cf[3L * c + ch + e] : 0.f;
+    ky[e] = in ? (float)cf[4L * c + ch + e] : 0.f;
+  }
+  const float* bx = x + img * hw * ldx + ch;
+  const float* by = y + img * hw * ldy + ch;
+  float* bd = dx + img * hw * ldd + ch;
+  const long p0 = (long)blockIdx.x * ty * TAPB_RUN;
+#pragma unroll
+  for (int r = 0; r < TAPB_RUN; ++r) {
+    const long p = p0 + py + (long)ty * r;
+    if (p >= hw) break;
+    const f32x4 a = ld4<WIDE>(bx + p * ldx, c, ch);
+    const f32x4 b = ld4<WIDE>(by + p * ldy, c, ch);
+    const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      o[e] = (float)((A[e] + B[e] * (double)(bv[e] - ky[e])) + C[e] * (double)(av[e] - kx[e]));
+    float* q = bd + p * ldd;
+    if constexpr (WIDE) {
+      f32x4 v = {o[0], o[1], o[2], o[3]};
+      if (accumulate) v += *reinterpret_cast<const f32x4*>(q);
+      *reinterpret_cast<f32x4*>(q) = v;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (ch + e < c) q[e] = accumulate ? q[e] + o[e] : o[e];
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int rdeic_dists_prep_float(const void* img, int32_t ld, int32_t dtype, int64_t npix, float* raw,
+                                      float* norm, void* stream) {
+  if (!img || !raw || !norm || npix <= 0 || ld < 3 || dtype < 0 || dtype > 1 ||
+      (((uintptr_t)raw | (uintptr_t)norm) & 15))
+    return RDEIC_EINVAL;
+  const dim3 grid((unsigned)std::min<long>((npix + 255) / 256, 65536));
+  if (dtype == 1)
+    hipLaunchKernelGGL(dists_prep_float_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)img, ld,
+                       (long)npix, DISTS_AFFINE, raw, norm);
+  else
+    hipLaunchKernelGGL(dists_prep_float_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)img, ld,
+                       (long)npix, DISTS_AFFINE, raw, norm);
+  return launch_status();
+}
+
+extern "C" int rdeic_dists_prep_bwd(const float* dnorm, int32_t ld_dnorm, const float* draw, int32_t ld_draw,
+                                    int64_t npix, void* dpred, int32_t ld_dpred, int32_t dtype, void* stream) {
+  if (!dnorm || !draw || !dpred || npix <= 0 || ld_dnorm < 4 || ld_draw < 4 || ld_dnorm % 4 || ld_draw % 4 ||
+      ld_dpred < 3 || dtype < 0 || dtype > 1 || (((uintptr_t)dnorm | (uintptr_t)draw) & 15))
+    return RDEIC_EINVAL;
+  const dim3 grid((unsigned)std::min<long>((npix + 255) / 256, 65536));
+  if (dtype == 1)
+    hipLaunchKernelGGL(dists_prep_bwd_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, dnorm, ld_dnorm, draw,
+                       ld_draw, (long)npix, DISTS_AFFINE, (bf16*)dpred, ld_dpred);
+  else
+    hipLaunchKernelGGL(dists_prep_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, dnorm, ld_dnorm, draw,
+                       ld_draw, (long)npix, DISTS_AFFINE, (float*)dpred, ld_dpred);
+  return launch_status();
+}
+
+extern "C" int rdeic_dists_l2pool_bwd(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ld_x,
+                                      const float* y, int32_t ld_y, const float* dy, int32_t ld_dy, float* dx,
+                                      int32_t ld_dx, void* stream) {
+  if (!x || !y || !dy || !dx || n <= 0 || h <= 0 || w <= 0 || c <= 0 || ld_x < c || ld_y < c || ld_dy < c ||
+      ld_dx < c)
+    return RDEIC_EINVAL;
+  const int ho = (h + 1) / 2, wo = (w + 1) / 2;
+  const bool v4 = c % 4 == 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && ld_dy % 4 == 0 && ld_dx % 4 == 0 &&
+                  !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dx) & 15);
+  const long total = (long)n * h * w * (v4 ? c / 4 : c);
+  const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1L << 20));
+  if (v4)
+    hipLaunchKernelGGL(l2pool_bwd_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, h, w, c, ld_x, y, ld_y, dy,
+                       ld_dy, ho, wo, dx, ld_dx, total);
+  else
+    hipLaunchKernelGGL(l2pool_bwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, h, w, c, ld_x, y, ld_y, dy,
+                       ld_dy, ho, wo, dx, ld_dx, total);
+  return launch_status();
+}
+
+extern "C" int rdeic_dists_score_bwd(const double* mom, const double* alpha, const double* beta, const double* gs,
+                                     int32_t n, int64_t hw, int32_t c, double* coef, void* stream) {
+  if (!mom || !alpha || !beta || !gs || !coef || n <= 0 || n > 65535 || hw <= 0 || c <= 0) return RDEIC_EINVAL;
+  hipLaunchKernelGGL(dists_score_bwd_kernel, dim3((unsigned)((c + 255) / 256), n), dim3(256), 0, (hipStream_t)stream,
+                     mom, alpha, beta, gs, c, (double)hw, coef);
+  return launch_status();
+}
+
+extern "C" int rdeic_dists_tap_bwd(const float* x, int32_t ldx, const float* y, int32_t ldy, const double* coef,
+                                   int32_t n, int64_t hw, int32_t c, int32_t accumulate, float* dx, int32_t ld_dx,
+                                   void* stream) {
+  if (!x || !y || !coef || !dx || n <= 0 || n > 65535 || hw <= 0 || c <= 0 || ldx < c || ldy < c || ld_dx < c)
+    return RDEIC_EINVAL;
+  const MomGeom g = mom_geom(hw, c);  // tx, ty and the channel blocks; the pixel chunks are this kernel's own
+  const long nchunk = (hw + (long)g.ty * TAPB_RUN - 1) / ((long)g.ty * TAPB_RUN);
+  if (nchunk > 0x7fffffffL || g.cblocks > 65535) return RDEIC_EINVAL;
+  const bool wide = c % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ld_dx % 4 == 0 &&
+                    !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)dx) & 15);
+  const dim3 grid((unsigned)nchunk, g.cblocks, n);
+  if (wide)
+    hipLaunchKernelGGL(dists_tap_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, coef,
+                       (long)hw, c, g.tx, accumulate, dx, ld_dx);
+  else
+    hipLaunchKernelGGL(dists_tap_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, coef,
+                       (long)hw, c, g.tx, accumulate, dx, ld_dx);
+  return launch_status();
+}
 
 extern "C" int rdeic_dists_prep(const uint8_t* img, int32_t n, int32_t h, int32_t w, float* raw, float* norm,
                                 void* stream) {

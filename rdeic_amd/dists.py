@@ -1,4 +1,5 @@
-"""DISTS (Ding, Ma, Wang, Simoncelli 2020) on the device, the metric forward only.
+"""DISTS (Ding, Ma, Wang, Simoncelli 2020) on the device: the metric, and the training loss DISTS.loss with its
+backward (float images in [-1, 1], gradient to the prediction; the kernels' formulas are in DESIGN §25).
 
 The network is the VGG16 feature stack LPIPS("vgg") runs (the library's fp32 convs, ReLU in the epilogue), with
 an L2 Hanning pool where VGG has its max pools, the input image itself as a sixth (first) tap, and per tap and
@@ -196,7 +197,8 @@ def tap_score(mom: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, out: O
 
 
 class DISTS:
-    """DISTS(weights, backbone)(pred_u8, target_u8): uint8 [N, H, W, 3] device tensors -> float64 numpy [N]."""
+    """DISTS(weights, backbone)(pred_u8, target_u8): uint8 [N, H, W, 3] device tensors -> float64 numpy [N].
+    DISTS(weights, backbone).loss(pred, target): the training loss of float images in [-1, 1], differentiable in pred."""
 
     def __init__(self, weights=None, backbone=None, device="cuda"):
         if weights is None:
@@ -205,6 +207,8 @@ class DISTS:
         wsd = _load_file(weights) if isinstance(weights, (str, os.PathLike)) else weights
         alpha, beta = load_weights(wsd)
         raw = load_backbone(wsd if backbone is None else backbone)
+        self._raw = raw  # CPU masters; the backward's device copies are made on first use
+        self._bwd = None
         layers = _lpips.conv_layers("vgg")
         self.convs = []
         for i, (wt, b) in enumerate(raw):
@@ -257,3 +261,183 @@ class DISTS:
         for s0 in range(0, n, max(1, step)):
             self._chunk(pred_u8[s0:s0 + step], target_u8[s0:s0 + step], out[s0:s0 + step])
         return 1.0 - out.cpu().numpy()
+
+    # ------------------------------------------------------------------ training loss
+    def _bwd_weights(self):
+        """(conv1's weight as [kh][kw][4][cout] for the gather dgrad, the other convs packed for the input-gradient
+        conv: flipped, [cin][kh kw cout] as a stride-1 conv with pad k - 1 - p). Packed on first use and owned by
+        this instance: they go when it goes."""
+        if self._bwd is None:
+            self._bwd = _lpips.pack_bwd_weights(self._raw, "vgg", self.device)
+        return self._bwd
+
+    def forward_acts(self, x: torch.Tensor):
+        """Every activation of the normalised prep output x [n, h, w, 4], x first, and the index of each of the
+        five backbone taps in that list."""
+        acts, taps, ci = [x], [], 0
+        with ops.splitk_as((False, False)):
+            for op in _TABLE:
+                if op[0] == "conv":
+                    acts.append(ops.conv2d(acts[-1], self.convs[ci], act=ops.LEAKY, slope=0.0))
+                    ci += 1
+                elif op[0] == "pool":
+                    acts.append(l2_pool(acts[-1]))
+                else:
+                    taps.append(len(acts) - 1)
+        return acts, taps
+
+    def features_float(self, img: torch.Tensor) -> List[torch.Tensor]:
+        """The six taps of float [n, H, W, 3] images in [-1, 1] (tap 0: (v + 1) / 2, 4 channels, the last zero)."""
+        raw, x = prep_float(img)
+        acts, taps = self.forward_acts(x)
+        return [raw] + [acts[i] for i in taps]
+
+    def loss(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """mean_n D_n, D_n = 1 - sum_k sum_c (alpha_c S1_c + beta_c S2_c), of float NHWC device images [N, H, W, 3]
+        in [-1, 1] (not clamped), fp32 or bf16, as an fp32 device scalar. The gradient goes to pred only; the
+        backbone runs in fp32 whatever the image dtype."""
+        for t in (pred, target):
+            if t.dim() != 4 or t.shape[3] != 3 or t.dtype not in (torch.float32, torch.bfloat16) or not t.is_cuda:
+                raise ValueError("DISTS.loss: float32 / bfloat16 [N, H, W, 3] device images expected")
+        if pred.shape != target.shape or pred.numel() == 0:
+            raise ValueError("DISTS.loss: prediction and target must share a non-empty shape")
+        n, h, w, _ = pred.shape
+        if n > 2 * MAX_PAIRS - 1 or n * image_bytes(h, w) >= MAX_TENSOR_BYTES:  # one backbone launch per side
+            raise ValueError(f"DISTS.loss at {h}x{w}: {n} images' activations ({n * image_bytes(h, w)} bytes) reach "
+                             f"2^31 bytes in one launch")
+        return _LossFn.apply(pred, target.detach(), self)
+
+
+class _LossFn(torch.autograd.Function):
+    """DISTS.loss: forward and backward on the kernels of dists.hip and the fp32 convs; torch only sequences."""
+
+    @staticmethod
+    def forward(ctx, pred, target, model: "DISTS"):
+        n = pred.shape[0]
+        f1 = model.features_float(target)  # the target's other activations are dropped at once
+        raw, x = prep_float(pred)
+        acts, taps = model.forward_acts(x)
+        out = torch.empty(n, dtype=torch.float64, device=pred.device)
+        moms = []
+        for k, a in enumerate([raw] + [acts[i] for i in taps]):
+            moms.append(moments(a, f1[k]))
+            tap_score(moms[-1], model.alpha[k], model.beta[k], out=out, accumulate=k > 0)
+        ctx.save_for_backward(raw, *acts, *f1, *moms)  # kept until the graph is freed: backward may run again
+        ctx.model, ctx.n_acts = model, len(acts)
+        ctx.pred_meta = (tuple(pred.shape), pred.dtype)
+        ctx.splitk = ops.splitk_state()  # the backward runs on autograd's thread: the dgrads split K as allowed here
+        return (1.0 - out).mean().to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        model, saved = ctx.model, ctx.saved_tensors
+        na = ctx.n_acts
+        raw, acts, f1, moms = saved[0], saved[1:1 + na], saved[1 + na:7 + na], saved[7 + na:]
+        (n, h, w, _), dtype = ctx.pred_meta
+        gs = (-gout.to(torch.float64) / n).expand(n).contiguous()  # d loss / d score_n
+        w0, packs = model._bwd_weights()
+        recs, i, ci, k = [], 0, 0, 1  # forward records: (op, activation index of its input)
+        for op in _TABLE:
+            if op[0] == "tap":
+                recs.append(("tap", i, k))
+                k += 1
+            else:
+                recs.append((op, i, ci))
+                i += 1
+                ci += op[0] == "conv"
+        d = dpred = None
+        with ops.splitk_as(ctx.splitk):
+            for op, i, j in reversed(recs):
+                if op == "tap":
+                    d = tap_bwd(acts[i], f1[j], moms[j], model.alpha[j], model.beta[j], gs, out=d)
+                elif op[0] == "pool":
+                    d = l2_pool_bwd(acts[i], acts[i + 1], d)
+                elif j == 0:
+                    _, _, cout, ks, s, p = op
+                    dnorm = _lpips.conv_dgrad_small(d, acts[1], w0, (h, w), 4, ks, s, p, prep_bwd=False)
+                    draw = tap_bwd(raw, f1[0], moms[0], model.alpha[0], model.beta[0], gs)
+                    dpred = prep_bwd(dnorm, draw, dtype)
+                else:
+                    _, _, cout, ks, s, p = op
+                    z = acts[i + 1]
+                    ops.call("rdeic_act_bwd", d.data_ptr(), ops.pix_ld(d), z.data_ptr(), ops.pix_ld(z),
+                             d.numel() // cout, cout, ops.LEAKY, 0.0, d.data_ptr(), ops.pix_ld(d), 0,
+                             ops.stream_ptr())  # the ReLU mask, in place
+                    d = ops.conv2d(d, packs[j], out_hw=tuple(acts[i].shape[1:3]))  # stride 1 throughout
+        return dpred, None, None
+
+
+def prep_float(img: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Float NHWC [n, h, w, 3] in [-1, 1] (fp32 / bf16, any pixel stride) -> (raw, normalised), both fp32
+    [n, h, w, 4] with a zero fourth channel: r = v * 0.5 + 0.5, then (r - mean_c) / std_c."""
+    n, h, w, _ = img.shape
+    raw = torch.empty((n, h, w, 4), dtype=torch.float32, device=img.device)
+    norm = torch.empty((n, h, w, 4), dtype=torch.float32, device=img.device)
+    try:
+        ld = ops.pix_ld(img)
+    except ValueError:
+        img = img.contiguous()
+        ld = 3
+    ops.call("rdeic_dists_prep_float", img.data_ptr(), ld, ops.dt_code(img), n * h * w, raw.data_ptr(),
+             norm.data_ptr(), ops.stream_ptr())
+    return raw, norm
+
+
+def prep_bwd(dnorm: torch.Tensor, draw: torch.Tensor, dtype=torch.float32,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The image gradient [n, h, w, 3] (fp32 / bf16) of prep_float from the fp32 4-channel gradients of its two
+    outputs: 0.5 * (dnorm_c / std_c + draw_c)."""
+    if dnorm.shape != draw.shape or dnorm.dim() != 4 or dnorm.shape[3] != 4 or dnorm.dtype != torch.float32 \
+            or draw.dtype != torch.float32:
+        raise ValueError("prep_bwd: two fp32 [n, h, w, 4] gradients of one shape expected")
+    n, h, w, _ = dnorm.shape
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=dtype, device=dnorm.device)
+    elif tuple(out.shape) != (n, h, w, 3):
+        raise ValueError(f"prep_bwd: out must be {(n, h, w, 3)}")
+    ops.call("rdeic_dists_prep_bwd", dnorm.data_ptr(), ops.pix_ld(dnorm), draw.data_ptr(), ops.pix_ld(draw),
+             n * h * w, out.data_ptr(), ops.pix_ld(out), ops.dt_code(out), ops.stream_ptr())
+    return out
+
+
+def l2_pool_bwd(x: torch.Tensor, y: torch.Tensor, dy: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Input gradient of y = l2_pool(x) (y the stored forward output): dx_j = x_j sum_o g_(o,j) dy_o / y_o."""
+    n, h, w, c = x.shape
+    so = (n, (h + 1) // 2, (w + 1) // 2, c)
+    if min(n, h, w, c) < 1 or tuple(y.shape) != so or tuple(dy.shape) != so \
+            or any(t.dtype != torch.float32 for t in (x, y, dy)):
+        raise ValueError(f"l2_pool_bwd: fp32 x [n, h, w, c] and y, dy {so} expected")
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    elif out.shape != x.shape or out.dtype != torch.float32:
+        raise ValueError(f"l2_pool_bwd: out must be fp32 {tuple(x.shape)}")
+    ops.call("rdeic_dists_l2pool_bwd", x.data_ptr(), n, h, w, c, ops.pix_ld(x), y.data_ptr(), ops.pix_ld(y),
+             dy.data_ptr(), ops.pix_ld(dy), out.data_ptr(), ops.pix_ld(out), ops.stream_ptr())
+    return out
+
+
+def tap_bwd(x: torch.Tensor, y: torch.Tensor, mom: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor,
+            gs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gs[n] * d tap_score(moments(x, y), alpha, beta)[n] / d x, written to a new tensor or added to out. gs: fp64
+    [n] on the device. Two launches: the fp64 coefficients per (image, channel), then the element-wise apply."""
+    if x.shape != y.shape or x.dim() != 4 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError("tap_bwd: two non-empty fp32 [n, h, w, c] maps of one shape expected")
+    n, h, w, c = x.shape
+    for v in (alpha, beta):
+        if v.dtype != torch.float64 or v.numel() != c or not v.is_contiguous():
+            raise ValueError(f"tap_bwd: alpha and beta must be {c} contiguous fp64 weights")
+    if mom.dtype != torch.float64 or tuple(mom.shape) != (n, 5, c) or not mom.is_contiguous():
+        raise ValueError(f"tap_bwd: contiguous fp64 moments {(n, 5, c)} expected")
+    if gs.dtype != torch.float64 or tuple(gs.shape) != (n,) or not gs.is_contiguous():
+        raise ValueError(f"tap_bwd: gs must be contiguous fp64 [{n}]")
+    acc = out is not None
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    elif out.shape != x.shape or out.dtype != torch.float32:
+        raise ValueError(f"tap_bwd: out must be fp32 {tuple(x.shape)}")
+    coef = torch.empty((n, 5, c), dtype=torch.float64, device=x.device)
+    ops.call("rdeic_dists_score_bwd", mom.data_ptr(), alpha.data_ptr(), beta.data_ptr(), gs.data_ptr(), n, h * w, c,
+             coef.data_ptr(), ops.stream_ptr())
+    ops.call("rdeic_dists_tap_bwd", x.data_ptr(), ops.pix_ld(x), y.data_ptr(), ops.pix_ld(y), coef.data_ptr(), n,
+             h * w, c, int(acc), out.data_ptr(), ops.pix_ld(out), ops.stream_ptr())
+    return out

@@ -43,8 +43,9 @@ class FineTuneConfig:
 
     def __init__(self, learning_rate=2e-5, l_guide_weight=3.0, l_bpp_weight=1.0, used_timesteps=300,
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, vq_beta=0.25, vq_decay=0.99, vq_temp=0.07,
-                 is_refine=False, fixed_step=2):
+                 is_refine=False, fixed_step=2, l_dists_weight=0.0):
         self.is_refine, self.fixed_step = bool(is_refine), int(fixed_step)  # configs/model/rdeic.yaml: True, 2
+        self.l_dists_weight = float(l_dists_weight)  # refine only: + l_guide_weight * l_dists_weight * DISTS.loss
         self.learning_rate = learning_rate
         self.l_guide_weight = l_guide_weight
         self.l_bpp_weight = l_bpp_weight
@@ -70,9 +71,10 @@ class FineTuner:
     """Holds the flat trainable parameters / grads / AdamW state of an RDEIC model and runs steps."""
 
     def __init__(self, model: RDEIC, cfg: Optional[FineTuneConfig] = None,
-                 embed_prob: Optional[torch.Tensor] = None, lpips=None):
+                 embed_prob: Optional[torch.Tensor] = None, lpips=None, dists=None):
         """lpips: an rdeic_amd.lpips.LPIPS (the reference's LPIPS(pnet_type='alex'), model/rdeic.py:653), needed by
         the refine step (cfg.is_refine) only.
+        dists: an rdeic_amd.dists.DISTS, needed where cfg.l_dists_weight > 0 (the refine step's opt-in DISTS term).
         embed_prob: the VectorQuantiser's codebook-usage EMA buffer
         (`preprocess_model.quantize.embed_prob` of a reference checkpoint or of train.py's own; zeros
         when absent, as a freshly built VectorQuantiser, compression_modules.py:239-241). It sets which
@@ -83,6 +85,9 @@ class FineTuner:
         self.lpips = lpips
         if self.cfg.is_refine and lpips is None:
             raise ValueError("the refine step (is_refine) needs an LPIPS model: FineTuner(..., lpips=LPIPS('alex', ...))")
+        self.dists = dists
+        if self.cfg.l_dists_weight > 0 and dists is None:
+            raise ValueError("l_dists_weight > 0 needs a DISTS model: FineTuner(..., dists=DISTS(weights, backbone))")
         st = model.store
         self.dtype = st.compute_dtype
         dev = st.device
@@ -492,10 +497,16 @@ class FineTuner:
         loss = cfg.l_guide_weight * loss_mse.mean()
         loss_lpips = self.lpips.loss(image, target)
         loss = loss + cfg.l_guide_weight * loss_lpips * 0.5
+        loss_dists = None
+        if cfg.l_dists_weight > 0:  # opt-in; at 0 no DISTS code runs and the sum above is today's, to the bit
+            loss_dists = self.dists.loss(image, target)
+            loss = loss + cfg.l_guide_weight * cfg.l_dists_weight * loss_dists
         loss_guide = ((c_latent - x_start) ** 2).mean()
         loss = loss + cfg.l_guide_weight * loss_guide
         d = {"T/l_simple": loss_simple.mean(), "T/l_mse": loss_mse.mean(), "T/l_lpips": loss_lpips,
              "T/l_guide": loss_guide, "T/loss": loss, "T/l_bpp": bpp[0], "T/q_bpp": q_bpp[0], "T/l_emb": emb_loss[0]}
+        if loss_dists is not None:
+            d["T/l_dists"] = loss_dists
         loss = loss + cfg.l_bpp_weight * bpp[0]
         loss = loss + cfg.l_bpp_weight * emb_loss[0]
         self._last = dict(c_latent=c_latent.detach(), x_T=x_T.detach(), samples=samples, image=image,

@@ -246,16 +246,7 @@ class LPIPS:
         conv, autograd.conv_dgrad's form: flipped, [cin][kh kw cout] as a stride-1 conv with pad k - 1 - p).
         Packed on first use and owned by this instance: they go when it goes."""
         if self._bwd is None:
-            w0 = torch.nn.functional.pad(self._raw[0][0], (0, 0, 0, 0, 0, 1))
-            packs = [None]
-            for (w, _), (_, _, cin, cout, k, _, p) in zip(self._raw[1:], conv_layers(self.net)[1:]):
-                wd = w.to(self.device).contiguous()
-                wld = -(-(k * k * cout) // 64) * 64
-                packed = torch.empty((cin, wld), dtype=torch.float32, device=self.device)
-                ops.call("rdeic_pack_conv_weight_dgrad", wd.data_ptr(), cout, cin, k, k, packed.data_ptr(), wld, 0,
-                         ops.stream_ptr())
-                packs.append(ops.ConvParams(packed, wld, None, cin, cout, k, k, 1, k - 1 - p))
-            self._bwd = (w0.permute(2, 3, 1, 0).contiguous().to(self.device), packs)
+            self._bwd = pack_bwd_weights(self._raw, self.net, self.device)
         return self._bwd
 
     def forward_acts(self, x: torch.Tensor):
@@ -347,6 +338,21 @@ class _LossFn(torch.autograd.Function):
                              ops.stream_ptr())  # the ReLU mask, in place
                     d = ops.conv2d(d, packs[j], out_hw=tuple(acts[i].shape[1:3]))  # stride 1 throughout
         return dpred, None, None
+
+
+def pack_bwd_weights(raw, net: str, device):
+    """The backward's device weights of a backbone's raw [(weight, bias)] list (LPIPS and DISTS share it): conv1 as
+    [kh][kw][4][cout], and [None] + the other convs' flipped packs, each a stride-1 conv with pad k - 1 - p."""
+    w0 = torch.nn.functional.pad(raw[0][0], (0, 0, 0, 0, 0, 1))
+    packs = [None]
+    for (w, _), (_, _, cin, cout, k, _, p) in zip(raw[1:], conv_layers(net)[1:]):
+        wd = w.to(device).contiguous()
+        wld = -(-(k * k * cout) // 64) * 64
+        packed = torch.empty((cin, wld), dtype=torch.float32, device=device)
+        ops.call("rdeic_pack_conv_weight_dgrad", wd.data_ptr(), cout, cin, k, k, packed.data_ptr(), wld, 0,
+                 ops.stream_ptr())
+        packs.append(ops.ConvParams(packed, wld, None, cin, cout, k, k, 1, k - 1 - p))
+    return w0.permute(2, 3, 1, 0).contiguous().to(device), packs
 
 
 def prep_float(img: torch.Tensor) -> torch.Tensor:

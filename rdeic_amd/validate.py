@@ -28,7 +28,7 @@ def noise_seed(seed: int, index: int) -> int:
 
 class Validator:
     """run(global_step) -> {"global_step", "avg_bpp", "usage", "avg_psnr", "avg_ssim", "avg_ms_ssim",
-    ["avg_lpips"], "images", "bodies_sha256"}.
+    ["avg_lpips"], ["avg_dists"], "images", "bodies_sha256"}.
 
     loader: an ImageListLoader over the whole validation list (rank 0, world 1); the images of its first epoch
     order (all of them, or its whole batches with drop_last, at most limit_batches batches) are sharded over the
@@ -36,12 +36,13 @@ class Validator:
     whose parameters the model shares (sync_inference() runs first), or None for a model that is not training.
     usage is the fraction of VQ codes used over the epoch (compression_modules.py:221-226; the count restarts at
     every run, as on_validation_epoch_start), from the indices the decompress path decoded. last_rows
-    ([images][bpp, psnr, ssim, ms_ssim(, lpips)]) and last_bodies (this rank's) keep the latest run's detail."""
+    ([images][bpp, psnr, ssim, ms_ssim(, lpips)(, dists)]) and last_bodies (this rank's) keep the latest run's detail."""
 
-    def __init__(self, model, ft, loader, *, steps: int, sampler: str = "ddpm", lpips=None,
+    def __init__(self, model, ft, loader, *, steps: int, sampler: str = "ddpm", lpips=None, dists=None,
                  save_dir: Optional[str] = None, seed: int = 231, limit_batches: Optional[int] = None, context=None):
         self.model, self.ft, self.loader = model, ft, loader
         self.steps, self.sampler, self.lpips, self.save_dir = int(steps), sampler, lpips, save_dir
+        self.dists = dists  # an rdeic_amd.dists.DISTS: adds the per-image dists column and avg_dists, after LPIPS
         self.seed, self.limit_batches = int(seed), limit_batches
         self.context = context if context is not None else synth_context().to(model.device)
         self.last_rows = None
@@ -88,6 +89,8 @@ class Validator:
                 cols = [[8.0 * len(b) / (H * W_) for b in bodies], ps, ss, ms]
                 if self.lpips is not None:
                     cols.append(metrics.lpips(out, imgs, self.lpips))
+                if self.dists is not None:
+                    cols.append(metrics.dists(out, imgs, self.dists))
                 rows.append(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
                 bodies_all += list(bodies)
                 if saver:
@@ -99,7 +102,7 @@ class Validator:
         finally:
             if saver:
                 saver.shutdown(wait=True)
-        k = 5 if self.lpips is not None else 4
+        k = 4 + (self.lpips is not None) + (self.dists is not None)
         mine = torch.from_numpy(np.concatenate(rows) if rows else np.zeros((0, k))).to(torch.float32)
         digest = hashlib.sha256(b"".join(bodies_all)).hexdigest()
         if distributed:
@@ -116,6 +119,8 @@ class Validator:
                "avg_ms_ssim": float(avg[3])}
         if self.lpips is not None:
             rec["avg_lpips"] = float(avg[4])
+        if self.dists is not None:
+            rec["avg_dists"] = float(avg[k - 1])
         rec.update(images=int(len(allrows)), bodies_sha256=digest)  # this rank's bodies, in order
         return rec
 

@@ -16,7 +16,8 @@ dict, loaded with safe loaders only). With `is_refine: true` (configs/refine.yam
 configs/model/rdeic.yaml) the step is p_losses' refine branch: the relay sampler and the VAE decoder in the loop,
 image MSE + 0.5 LPIPS(alex); it needs model.lpips_backbone / model.lpips_lin and runs eagerly. Logs the reference's
 loss dict (T/loss, T/l_simple, T/l_bpp, T/q_bpp, T/l_emb, T/l_guide; refine: also T/l_mse, T/l_lpips) every
-log_every_n_steps and saves the trainable parameters (and the
+log_every_n_steps; with `model.l_dists_weight` > 0 (configs/refine_dists.yaml; needs model.dists_weights, optionally
+model.dists_backbone) the refine loss adds l_guide_weight * l_dists_weight * DISTS and T/l_dists is logged too. It saves the trainable parameters (and the
 AdamW state) every every_n_train_steps as safetensors.
 """
 from __future__ import annotations
@@ -122,6 +123,17 @@ def main(argv=None):
             if not mc.get(key) or not os.path.isfile(str(mc[key])):
                 raise SystemExit(f"is_refine: true needs model.{key}: the torchvision AlexNet state dict "
                                  f"(lpips_backbone) and the LPIPS lin heads (lpips_lin); got {mc.get(key)!r}")
+    l_dists = float(mc.get("l_dists_weight") or 0.0)
+    if l_dists > 0:  # the opt-in DISTS term of the refine loss; no weights ship with the project
+        if not refine:
+            raise SystemExit("model.l_dists_weight > 0 needs is_refine: true: the DISTS term is taken on the decoded "
+                             "image, which the non-refine step does not have")
+        if not mc.get("dists_weights") or not os.path.isfile(str(mc["dists_weights"])):
+            raise SystemExit(f"l_dists_weight: {l_dists} needs model.dists_weights: the DISTS alpha / beta file "
+                             f"(.pt / .pth / .npz; the VGG16 convs from it or from model.dists_backbone); got "
+                             f"{mc.get('dists_weights')!r}")
+        if mc.get("dists_backbone") and not os.path.isfile(str(mc["dists_backbone"])):
+            raise SystemExit(f"model.dists_backbone: no such file {mc['dists_backbone']!r}")
     rank, world, local = parallel.init_from_env()
     dev = torch.device("cuda", local)
     model = RDEIC(compute_dtype=dtype, device=dev).init_synthetic()
@@ -132,13 +144,18 @@ def main(argv=None):
     if refine:
         from rdeic_amd.lpips import LPIPS
         lpips = LPIPS("alex", backbone=str(mc["lpips_backbone"]), lin=str(mc["lpips_lin"]), device=dev)
+    dists = None
+    if l_dists > 0:
+        from rdeic_amd.dists import DISTS
+        dists = DISTS(str(mc["dists_weights"]), backbone=str(mc["dists_backbone"]) if mc.get("dists_backbone") else None,
+                      device=dev)
     # the codebook-usage EMA travels with the weights (reference checkpoints and ours)
     ft = FineTuner(model, FineTuneConfig(learning_rate=float(mc["learning_rate"]),
                                          l_guide_weight=float(mc["l_guide_weight"]),
                                          l_bpp_weight=float(mc["l_bpp_weight"]),
                                          used_timesteps=int(mc["used_timesteps"]), is_refine=refine,
-                                         fixed_step=int(mc.get("fixed_step", 2))),
-                   embed_prob=sd.get(EMBED_PROB), lpips=lpips)
+                                         fixed_step=int(mc.get("fixed_step", 2)), l_dists_weight=l_dists),
+                   embed_prob=sd.get(EMBED_PROB), lpips=lpips, dists=dists)
     start = 0
     if "optimizer.exp_avg" in sd:  # one of train.py's own checkpoints: continue that run exactly
         start = int(meta.get("global_step", 0))
@@ -170,7 +187,7 @@ def main(argv=None):
         from rdeic_amd.validate import Validator
         save = bool((cfg.get("validation") or {}).get("save_images", False))
         validator = Validator(model, ft, val_loader, steps=ft.cfg.fixed_step if refine else 5, sampler="ddpm",
-                              lpips=lpips, save_dir=ck_dir if save else None, seed=seed,
+                              lpips=lpips, dists=dists, save_dir=ck_dir if save else None, seed=seed,
                               limit_batches=tr.get("limit_val_batches"), context=ctx)
     graph = None
     records = []
