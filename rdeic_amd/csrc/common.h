@@ -83,6 +83,25 @@ __device__ __forceinline__ float warp_max(float v) {
   return v;
 }
 
+// torch's max_pool2d comparison: a NaN wins and stays
+__device__ __forceinline__ float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }
+
+// A group of 4 channels at p, the channels ch .. ch + 3 of c: one 16-byte load where WIDE (c % 4 == 0, ld % 4 == 0,
+// aligned bases); else element-wise, a tail group of fewer than 4 channels reading zeros past c.
+template <bool WIDE>
+__device__ __forceinline__ f32x4 ld4(const float* __restrict__ p, int c, int ch) {
+  if constexpr (WIDE) {
+    return *reinterpret_cast<const f32x4*>(p);
+  } else {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    v.x = p[0];
+    if (ch + 1 < c) v.y = p[1];
+    if (ch + 2 < c) v.z = p[2];
+    if (ch + 3 < c) v.w = p[3];
+    return v;
+  }
+}
+
 static inline int launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? RDEIC_OK : RDEIC_ELAUNCH;

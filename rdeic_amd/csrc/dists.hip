@@ -115,20 +115,6 @@ MomGeom mom_geom(long hw, int c) {
   return g;
 }
 
-template <bool WIDE>
-__device__ __forceinline__ f32x4 ld4(const float* __restrict__ p, int c, int ch) {
-  if constexpr (WIDE) {
-    return *reinterpret_cast<const f32x4*>(p);
-  } else {  // a tail group of fewer than 4 channels reads zeros past c
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    v.x = p[0];
-    if (ch + 1 < c) v.y = p[1];
-    if (ch + 2 < c) v.z = p[2];
-    if (ch + 3 < c) v.w = p[3];
-    return v;
-  }
-}
-
 // Adds the Q x 4 fp64 sums of the block's threads that share a channel group, in a fixed order: the butterfly
 // over the pixel rows inside a wave (lanes tx apart), then the four waves in order. Returns true for the
 // threads (wave 0, lane < tx) that hold the result.

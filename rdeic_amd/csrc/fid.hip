@@ -69,9 +69,6 @@ __global__ __launch_bounds__(256) void fid_prep_kernel(const uint8_t* __restrict
 }
 
 // ---------------------------------------------------------------- pool2d
-// torch's max_pool2d comparison: a NaN wins and stays
-__device__ __forceinline__ float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }
-
 // one thread per V channels of one output pixel; V = 4 needs c, both ld % 4 == 0 and 16-byte bases
 template <int V, bool AVG>
 __global__ __launch_bounds__(256) void pool2d_kernel(const float* __restrict__ in, int h, int w, int c, int ld_in,
@@ -125,21 +122,6 @@ __global__ __launch_bounds__(256) void pool2d_kernel(const float* __restrict__ i
 // ---------------------------------------------------------------- global average pool
 constexpr int GAP_TX = 64;  // channel groups (of 4) across a block
 constexpr int GAP_L = 4;    // pixel lanes: lane l adds the pixels l, l + GAP_L, ... in order
-
-// a group of 4 channels; a tail group of fewer reads zeros past c
-template <bool WIDE>
-__device__ __forceinline__ f32x4 ld4(const float* __restrict__ p, int c, int ch) {
-  if constexpr (WIDE) {
-    return *reinterpret_cast<const f32x4*>(p);
-  } else {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    v.x = p[0];
-    if (ch + 1 < c) v.y = p[1];
-    if (ch + 2 < c) v.z = p[2];
-    if (ch + 3 < c) v.w = p[3];
-    return v;
-  }
-}
 
 // grid (channel blocks, n), 256 threads = GAP_L pixel lanes (one wave each) by GAP_TX channel groups
 template <bool WIDE>

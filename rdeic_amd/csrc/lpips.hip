@@ -57,10 +57,8 @@ __global__ __launch_bounds__(256) void lpips_prep_kernel(const uint8_t* __restri
   }
 }
 
-// torch's max_pool2d comparison: a NaN wins and stays
-__device__ __forceinline__ float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }
-
-// one thread per V output channels of one output pixel; V = 4 needs c, both ld % 4 == 0 and 16-byte bases
+// one thread per V output channels of one output pixel; V = 4 needs c, both ld % 4 == 0 and 16-byte bases.
+// The p = 0, max-only case of fid.hip's pool2d_kernel (the same bits); kept because it measured faster.
 template <int V>
 __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ in, int h, int w, int c, int ld_in,
                                                       int k, int s, int ho, int wo, float* __restrict__ out,

@@ -20,17 +20,16 @@ only. The batch is therefore chunked freely (chunk_pairs) to keep every activati
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
-from . import _lib, lpips as _lpips, ops
+from . import _lib, lpips as _lpips, ops, tower
 
 CHANNELS = (3, 64, 128, 256, 512, 512)  # per tap; the image itself first
 N_WEIGHTS = sum(CHANNELS)  # 1475
-MAX_TENSOR_BYTES = 2 ** 31
+MAX_TENSOR_BYTES = tower.MAX_TENSOR_BYTES
 MAX_PAIRS = 32768  # per launch: rdeic_dists_moments takes at most 65535 images
 _TABLE = _lpips.NETS["vgg"]  # ("conv", ...) / ("pool", 2, 2) / ("tap",): the pools become L2 pools here
 
@@ -70,35 +69,21 @@ def image_bytes(h: int, w: int) -> int:
 
 
 def chunk_pairs(h: int, w: int) -> int:
-    """Image pairs per backbone launch, a function of (H, W) alone: the most for which every activation of the
-    2 x pairs images stays under 2^31 bytes, at least 1 (then split_pair may still apply) and at most MAX_PAIRS
-    (the moment kernels take the image from the grid's third dimension). An image whose own activations reach
-    2^31 bytes is refused."""
-    per = image_bytes(h, w)
-    if per >= MAX_TENSOR_BYTES:
-        raise ValueError(f"DISTS at {h}x{w}: one image's activation reaches 2^31 bytes")
-    return min(MAX_PAIRS, max(1, ((MAX_TENSOR_BYTES - 1) // per) // 2))
+    """Image pairs per backbone launch, a function of (H, W) alone (tower.chunk_pairs), at most MAX_PAIRS (the
+    moment kernels take the image from the grid's third dimension). An image whose own activations reach 2^31
+    bytes is refused."""
+    return tower.chunk_pairs(image_bytes(h, w), MAX_PAIRS, who=f"DISTS at {h}x{w}")
 
 
 def split_pair(h: int, w: int) -> bool:
     """True where even one pair's activations would reach 2^31 bytes in one launch."""
-    return 2 * image_bytes(h, w) >= MAX_TENSOR_BYTES
-
-
-def _load_file(path: str) -> Dict[str, torch.Tensor]:
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"DISTS weights not found: {path}")
-    if str(path).endswith(".npz"):
-        with np.load(path) as z:
-            return {k: torch.from_numpy(np.array(z[k])) for k in z.files}
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    return sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+    return tower.split_pair(image_bytes(h, w))
 
 
 def load_weights(src: Union[str, Dict]) -> Tuple[np.ndarray, np.ndarray]:
     """(alpha, beta) as float64 [1475] from a path (.pt / .pth / .npz) or a dict holding `alpha` and `beta`,
     [1, 1475, 1, 1] or flat."""
-    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    sd = tower.load_state(src, "DISTS")
     out = []
     for name in ("alpha", "beta"):
         if name not in sd:
@@ -114,7 +99,7 @@ def load_backbone(src: Union[str, Dict[str, torch.Tensor]]) -> List[Tuple[torch.
     """[(weight [cout,cin,3,3], bias [cout])] fp32 CPU tensors of the 13 convs, in order, from the torchvision
     VGG16 state dict (features.<i>.*), the lpips package's (net.slice<k>.<i>.*), or the single-file layout
     stage<k>.<i>.* (<i> the torchvision features index)."""
-    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    sd = tower.load_state(src, "DISTS")
     layers = _lpips.conv_layers("vgg")
     stage = [f"stage{k}.{i}" for i, k, *_ in layers]
     if all(f"{n}.weight" in sd and f"{n}.bias" in sd for n in stage):
@@ -196,26 +181,21 @@ def tap_score(mom: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, out: O
     return out
 
 
-class DISTS:
+def _pool(x: torch.Tensor, op) -> torch.Tensor:
+    return l2_pool(x)
+
+
+class DISTS(tower.Backbone):
     """DISTS(weights, backbone)(pred_u8, target_u8): uint8 [N, H, W, 3] device tensors -> float64 numpy [N].
     DISTS(weights, backbone).loss(pred, target): the training loss of float images in [-1, 1], differentiable in pred."""
 
     def __init__(self, weights=None, backbone=None, device="cuda"):
         if weights is None:
             raise ValueError("DISTS needs its alpha / beta weights and a VGG16 backbone; none ship with the project")
-        self.device = torch.device(device)
-        wsd = _load_file(weights) if isinstance(weights, (str, os.PathLike)) else weights
+        wsd = tower.load_state(weights, "DISTS")
         alpha, beta = load_weights(wsd)
-        raw = load_backbone(wsd if backbone is None else backbone)
-        self._raw = raw  # CPU masters; the backward's device copies are made on first use
-        self._bwd = None
-        layers = _lpips.conv_layers("vgg")
-        self.convs = []
-        for i, (wt, b) in enumerate(raw):
-            if i == 0:  # zero fourth input channel (the prep kernel's): exact zero products, 16-byte gathers
-                wt = torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, 1))
-            _, _, _, _, _, s, p = layers[i]
-            self.convs.append(ops.ConvParams.pack(wt, b, stride=s, pad=p, dtype=torch.float32))
+        self.table = _TABLE
+        super().__init__(load_backbone(wsd if backbone is None else backbone), _lpips.conv_layers("vgg"), device)
         # normalised once in fp64; per tap, padded with zeros to the tap's stored channel count (4 at tap 0)
         total = alpha.sum() + beta.sum()
         self.alpha, self.beta, c0 = [], [], 0
@@ -227,64 +207,24 @@ class DISTS:
 
     def features(self, img_u8: torch.Tensor) -> List[torch.Tensor]:
         """The six taps [n, h_k, w_k, C_k] fp32 of uint8 [n, H, W, 3] images (tap 0: 4 channels, the last zero)."""
-        raw, x = prep(img_u8)
-        taps, ci = [raw], 0
-        with ops.splitk_as((False, False)):  # a k grouping that depended on the batch would break invariance
-            for op in _TABLE:
-                if op[0] == "conv":
-                    x = ops.conv2d(x, self.convs[ci], act=ops.LEAKY, slope=0.0)
-                    ci += 1
-                elif op[0] == "pool":
-                    x = l2_pool(x)
-                else:
-                    taps.append(x)
-        return taps
+        acts = list(prep(img_u8))  # [raw, normalised]: the walk alone holds the normalised image
+        raw = acts.pop(0)
+        return [raw] + tower.forward(self.table, self.convs, _pool, acts, keep_all=False)
 
-    def _chunk(self, pred: torch.Tensor, tgt: torch.Tensor, out: torch.Tensor) -> None:
-        n, h, w, _ = pred.shape
-        if split_pair(h, w):
-            f0, f1 = self.features(pred), self.features(tgt)
-        else:
-            f = self.features(torch.cat([pred, tgt]))
-            f0, f1 = [t[:n] for t in f], [t[n:] for t in f]
-        for k, (a, b) in enumerate(zip(f0, f1)):
-            tap_score(moments(a, b), self.alpha[k], self.beta[k], out=out, accumulate=k > 0)
+    def _score_tap(self, k: int, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> None:
+        tap_score(moments(a, b), self.alpha[k], self.beta[k], out=out, accumulate=k > 0)
 
     def __call__(self, pred_u8: torch.Tensor, target_u8: torch.Tensor, chunk: Optional[int] = None) -> np.ndarray:
         """chunk: pairs per backbone launch (default chunk_pairs(H, W)); it never changes a score."""
-        if pred_u8.shape != target_u8.shape or pred_u8.dim() != 4 or pred_u8.shape[3] != 3 \
-                or pred_u8.dtype != torch.uint8 or target_u8.dtype != torch.uint8:
-            raise ValueError("expected matching uint8 [N, H, W, 3] images")
-        n, h, w, _ = pred_u8.shape
-        step = min(chunk_pairs(h, w), int(chunk) if chunk else n) if n else 1  # validates the size
-        out = torch.empty(n, dtype=torch.float64, device=pred_u8.device)
-        for s0 in range(0, n, max(1, step)):
-            self._chunk(pred_u8[s0:s0 + step], target_u8[s0:s0 + step], out[s0:s0 + step])
+        out = tower.score_pairs(pred_u8, target_u8, chunk, chunk_pairs, split_pair,  # this module's, looked up now
+                                self.features, self._score_tap, torch.float64)
         return 1.0 - out.cpu().numpy()
 
     # ------------------------------------------------------------------ training loss
-    def _bwd_weights(self):
-        """(conv1's weight as [kh][kw][4][cout] for the gather dgrad, the other convs packed for the input-gradient
-        conv: flipped, [cin][kh kw cout] as a stride-1 conv with pad k - 1 - p). Packed on first use and owned by
-        this instance: they go when it goes."""
-        if self._bwd is None:
-            self._bwd = _lpips.pack_bwd_weights(self._raw, "vgg", self.device)
-        return self._bwd
-
     def forward_acts(self, x: torch.Tensor):
         """Every activation of the normalised prep output x [n, h, w, 4], x first, and the index of each of the
         five backbone taps in that list."""
-        acts, taps, ci = [x], [], 0
-        with ops.splitk_as((False, False)):
-            for op in _TABLE:
-                if op[0] == "conv":
-                    acts.append(ops.conv2d(acts[-1], self.convs[ci], act=ops.LEAKY, slope=0.0))
-                    ci += 1
-                elif op[0] == "pool":
-                    acts.append(l2_pool(acts[-1]))
-                else:
-                    taps.append(len(acts) - 1)
-        return acts, taps
+        return tower.forward(self.table, self.convs, _pool, [x], keep_all=True)
 
     def features_float(self, img: torch.Tensor) -> List[torch.Tensor]:
         """The six taps of float [n, H, W, 3] images in [-1, 1] (tap 0: (v + 1) / 2, 4 channels, the last zero)."""
@@ -296,11 +236,7 @@ class DISTS:
         """mean_n D_n, D_n = 1 - sum_k sum_c (alpha_c S1_c + beta_c S2_c), of float NHWC device images [N, H, W, 3]
         in [-1, 1] (not clamped), fp32 or bf16, as an fp32 device scalar. The gradient goes to pred only; the
         backbone runs in fp32 whatever the image dtype."""
-        for t in (pred, target):
-            if t.dim() != 4 or t.shape[3] != 3 or t.dtype not in (torch.float32, torch.bfloat16) or not t.is_cuda:
-                raise ValueError("DISTS.loss: float32 / bfloat16 [N, H, W, 3] device images expected")
-        if pred.shape != target.shape or pred.numel() == 0:
-            raise ValueError("DISTS.loss: prediction and target must share a non-empty shape")
+        tower.check_float_pair(pred, target, "DISTS.loss")
         n, h, w, _ = pred.shape
         if n > 2 * MAX_PAIRS - 1 or n * image_bytes(h, w) >= MAX_TENSOR_BYTES:  # one backbone launch per side
             raise ValueError(f"DISTS.loss at {h}x{w}: {n} images' activations ({n * image_bytes(h, w)} bytes) reach "
@@ -336,34 +272,16 @@ class _LossFn(torch.autograd.Function):
         (n, h, w, _), dtype = ctx.pred_meta
         gs = (-gout.to(torch.float64) / n).expand(n).contiguous()  # d loss / d score_n
         w0, packs = model._bwd_weights()
-        recs, i, ci, k = [], 0, 0, 1  # forward records: (op, activation index of its input)
-        for op in _TABLE:
-            if op[0] == "tap":
-                recs.append(("tap", i, k))
-                k += 1
-            else:
-                recs.append((op, i, ci))
-                i += 1
-                ci += op[0] == "conv"
-        d = dpred = None
+
+        def tap_grad(k, x, out=None):
+            return tap_bwd(x, f1[k], moms[k], model.alpha[k], model.beta[k], gs, out=out)
+
         with ops.splitk_as(ctx.splitk):
-            for op, i, j in reversed(recs):
-                if op == "tap":
-                    d = tap_bwd(acts[i], f1[j], moms[j], model.alpha[j], model.beta[j], gs, out=d)
-                elif op[0] == "pool":
-                    d = l2_pool_bwd(acts[i], acts[i + 1], d)
-                elif j == 0:
-                    _, _, cout, ks, s, p = op
-                    dnorm = _lpips.conv_dgrad_small(d, acts[1], w0, (h, w), 4, ks, s, p, prep_bwd=False)
-                    draw = tap_bwd(raw, f1[0], moms[0], model.alpha[0], model.beta[0], gs)
-                    dpred = prep_bwd(dnorm, draw, dtype)
-                else:
-                    _, _, cout, ks, s, p = op
-                    z = acts[i + 1]
-                    ops.call("rdeic_act_bwd", d.data_ptr(), ops.pix_ld(d), z.data_ptr(), ops.pix_ld(z),
-                             d.numel() // cout, cout, ops.LEAKY, 0.0, d.data_ptr(), ops.pix_ld(d), 0,
-                             ops.stream_ptr())  # the ReLU mask, in place
-                    d = ops.conv2d(d, packs[j], out_hw=tuple(acts[i].shape[1:3]))  # stride 1 throughout
+            d = tower.backward(tower.backward_plan(model.table, 1), acts, packs, tap_grad,
+                               lambda op, x, y, dy: l2_pool_bwd(x, y, dy))
+            _, _, _, ks, s, p = model.table[0]  # conv 0: the gather dgrad with its ReLU mask, then the raw tap
+            dnorm = _lpips.conv_dgrad_small(d, acts[1], w0, (h, w), 4, ks, s, p, prep_bwd=False)
+            dpred = prep_bwd(dnorm, tap_grad(0, raw), dtype)
         return dpred, None, None
 
 

@@ -33,12 +33,11 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, tower
 
 SIZE = 299
 FEATURES = 2048
 BN_EPS = 1e-3
-MAX_TENSOR_BYTES = 2 ** 31
 POOL_MAX, POOL_AVG = 0, 1
 SPLIT_MIN_K, SPLIT_CHAIN = 1024, 512
 
@@ -189,20 +188,10 @@ def image_bytes() -> int:
 
 
 # images per tower launch: a function of the constant 299 alone (and under the global pool's 65535)
-CHUNK = min(32768, (MAX_TENSOR_BYTES - 1) // image_bytes())
+CHUNK = min(32768, (tower.MAX_TENSOR_BYTES - 1) // image_bytes())
 
 
 # ---------------------------------------------------------------- weights
-def _load_file(path: str) -> Dict[str, torch.Tensor]:
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"Inception weights not found: {path}")
-    if str(path).endswith(".npz"):
-        with np.load(path) as z:
-            return {k: torch.from_numpy(np.array(z[k])) for k in z.files}
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    return sd.get("state_dict", sd) if isinstance(sd, dict) else sd
-
-
 def fold_bn(weight, gamma, beta, mean, var, eps: float = BN_EPS) -> Tuple[torch.Tensor, torch.Tensor]:
     """(weight', bias') float64 with BatchNorm(conv(x, weight)) == conv(x, weight') + bias' (inference mode)."""
     w, g, b, m, v = (torch.as_tensor(t).detach().to("cpu", torch.float64) for t in (weight, gamma, beta, mean, var))
@@ -214,7 +203,7 @@ def load_inception(src: Union[str, Dict]) -> Dict[str, Tuple[torch.Tensor, torch
     """{prefix: (weight [cout, cin, kh, kw], bias [cout])} fp32 CPU tensors with the BatchNorms folded in (in
     float64), from the torchvision-named state dict (<prefix>.conv.weight, <prefix>.bn.weight / .bias /
     .running_mean / .running_var); fc.* and AuxLogits.* are ignored. A path (.pt / .pth / .npz) or a dict."""
-    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    sd = tower.load_state(src, "Inception")
     out = {}
     for prefix, cin, cout, (kh, kw), _, _ in conv_layers():
         want = {"conv.weight": (cout, cin, kh, kw), "bn.weight": (cout,), "bn.bias": (cout,),
@@ -319,8 +308,8 @@ class InceptionV3:
         folded = load_inception(weights)
         for i, (prefix, _, _, _, stride, _) in enumerate(conv_layers()):
             w, b = folded[prefix]
-            if i == 0:  # zero fourth input channel (the prep kernel's): exact zero products, 16-byte gathers
-                w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 1))
+            if i == 0:
+                w = tower.pad_cin4(w)
             # the paddings differ per axis: every call passes pad_t / pad_l / out_hw itself
             self.convs[prefix] = ops.ConvParams.pack(w, b, stride=stride, dtype=torch.float32)
 

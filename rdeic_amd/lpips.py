@@ -19,13 +19,12 @@ batch is therefore chunked freely (chunk_pairs) to keep every activation tensor 
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, tower
 
 # (torchvision `features` index, cout, kernel, stride, pad) / ("pool", k, s) / ("tap",) in forward order.
 # The lpips package's slice<k> holds the modules between tap k-1 and tap k under their features index.
@@ -40,7 +39,7 @@ _VGG = (("conv", 0, 64, 3, 1, 1), ("conv", 2, 64, 3, 1, 1), ("tap",), ("pool", 2
 NETS = {"alex": _ALEX, "vgg": _VGG}
 CHANNELS = {"alex": (64, 192, 384, 256, 256), "vgg": (64, 128, 256, 512, 512)}
 MIN_SIZE = {"alex": 31, "vgg": 16}  # the smallest H, W at which every tap has at least one pixel
-MAX_TENSOR_BYTES = 2 ** 31
+MAX_TENSOR_BYTES = tower.MAX_TENSOR_BYTES
 
 
 def _table(net: str):
@@ -98,35 +97,20 @@ def image_bytes(net: str, h: int, w: int) -> int:
 
 
 def chunk_pairs(net: str, h: int, w: int) -> int:
-    """Image pairs per backbone launch, a function of (net, H, W) alone: the most for which every activation
-    of the 2 x pairs images stays under 2^31 bytes, at least 1. At 1 the two images of the pair may still be
-    too large together; __call__ then runs prediction and target through the backbone one after the other
-    (split_pair). An image whose own activations reach 2^31 bytes is refused."""
-    per = image_bytes(net, h, w)
-    if per >= MAX_TENSOR_BYTES:
-        raise ValueError(f"LPIPS({net}) at {h}x{w}: one image's activation reaches 2^31 bytes")
-    return max(1, ((MAX_TENSOR_BYTES - 1) // per) // 2)
+    """Image pairs per backbone launch, a function of (net, H, W) alone (tower.chunk_pairs); an image whose own
+    activations reach 2^31 bytes is refused."""
+    return tower.chunk_pairs(image_bytes(net, h, w), who=f"LPIPS({net}) at {h}x{w}")
 
 
 def split_pair(net: str, h: int, w: int) -> bool:
     """True where even one pair's activations would reach 2^31 bytes in one launch."""
-    return 2 * image_bytes(net, h, w) >= MAX_TENSOR_BYTES
-
-
-def _load_file(path: str) -> Dict[str, torch.Tensor]:
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"LPIPS weights not found: {path}")
-    if path.endswith(".npz"):
-        with np.load(path) as z:
-            return {k: torch.from_numpy(np.array(z[k])) for k in z.files}
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    return sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+    return tower.split_pair(image_bytes(net, h, w))
 
 
 def load_backbone(net: str, src: Union[str, Dict[str, torch.Tensor]]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
     """[(weight [cout,cin,k,k], bias [cout])] fp32 CPU tensors of every conv, in order, from the torchvision
     state dict (features.<i>.*) or the lpips package's (net.slice<k>.<i>.*)."""
-    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    sd = tower.load_state(src, "LPIPS")
     layers = conv_layers(net)
     layouts = ([f"features.{i}" for i, *_ in layers], [f"net.slice{k}.{i}" for i, k, *_ in layers])
     for names in layouts:
@@ -150,7 +134,7 @@ def load_backbone(net: str, src: Union[str, Dict[str, torch.Tensor]]) -> List[Tu
 def load_lin(net: str, src: Union[str, Dict[str, torch.Tensor]]) -> List[torch.Tensor]:
     """The five head vectors [C_k] fp32 (CPU): the reference's .pth layout (lin<k>.model.1.weight [1,C,1,1]),
     or an .npz / dict with lin0..lin4 (or <net>_lin0..<net>_lin4, the layout of tests/golden/lpips_lin.npz)."""
-    sd = _load_file(src) if isinstance(src, (str, os.PathLike)) else src
+    sd = tower.load_state(src, "LPIPS")
     out = []
     _table(net)
     for k, c in enumerate(CHANNELS[net]):
@@ -176,7 +160,11 @@ def seeded_backbone(net: str, seed: int = 0) -> Dict[str, torch.Tensor]:
     return sd
 
 
-class LPIPS:
+def _pool(x: torch.Tensor, op) -> torch.Tensor:
+    return max_pool(x, op[1], op[2])
+
+
+class LPIPS(tower.Backbone):
     """LPIPS(net)(pred_u8, target_u8): uint8 [N, H, W, 3] device tensors -> float64 numpy [N].
     LPIPS(net).loss(pred, target): the training loss of float images in [-1, 1], differentiable in pred."""
 
@@ -185,16 +173,8 @@ class LPIPS:
             raise ValueError("LPIPS needs a backbone (torchvision / lpips state dict) and the lin heads; "
                              "no backbone weights ship with the project")
         self.net = net
-        self.device = torch.device(device)
         self.table = _table(net)
-        self.convs = []
-        self._raw = load_backbone(net, backbone)  # CPU masters; the backward's device copies are made on first use
-        self._bwd = None
-        for i, (wt, b) in enumerate(self._raw):
-            if i == 0:  # zero fourth input channel (the prep kernel's): exact zero products, 16-byte gathers
-                wt = torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, 1))
-            _, _, _, _, _, s, p = conv_layers(net)[i]
-            self.convs.append(ops.ConvParams.pack(wt, b, stride=s, pad=p, dtype=torch.float32))
+        super().__init__(load_backbone(net, backbone), conv_layers(net), device)
         self.lin = [v.to(self.device) for v in load_lin(net, lin)]
 
     # ------------------------------------------------------------------ pieces
@@ -206,62 +186,21 @@ class LPIPS:
 
     def features(self, img_u8: torch.Tensor) -> List[torch.Tensor]:
         """The five taps [n, h_k, w_k, C_k] fp32 of uint8 [n, H, W, 3] images."""
-        x, taps, ci = self.prep(img_u8), [], 0
-        with ops.splitk_as((False, False)):  # a k grouping that depended on the batch would break invariance
-            for op in self.table:
-                if op[0] == "conv":
-                    x = ops.conv2d(x, self.convs[ci], act=ops.LEAKY, slope=0.0)
-                    ci += 1
-                elif op[0] == "pool":
-                    x = max_pool(x, op[1], op[2])
-                else:
-                    taps.append(x)
-        return taps
+        return tower.forward(self.table, self.convs, _pool, [self.prep(img_u8)], keep_all=False)
 
-    def _chunk(self, pred: torch.Tensor, tgt: torch.Tensor, out: torch.Tensor) -> None:
-        n, h, w, _ = pred.shape
-        if split_pair(self.net, h, w):
-            f0, f1 = self.features(pred), self.features(tgt)
-        else:
-            f = self.features(torch.cat([pred, tgt]))
-            f0, f1 = [t[:n] for t in f], [t[n:] for t in f]
-        for k, (a, b) in enumerate(zip(f0, f1)):
-            layer_distance(a, b, self.lin[k], out=out, accumulate=k > 0)
+    def _score_tap(self, k: int, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> None:
+        layer_distance(a, b, self.lin[k], out=out, accumulate=k > 0)
 
     def __call__(self, pred_u8: torch.Tensor, target_u8: torch.Tensor, chunk: Optional[int] = None) -> np.ndarray:
         """chunk: pairs per backbone launch (default chunk_pairs(net, H, W)); it never changes a score."""
-        if pred_u8.shape != target_u8.shape or pred_u8.dim() != 4 or pred_u8.shape[3] != 3 \
-                or pred_u8.dtype != torch.uint8 or target_u8.dtype != torch.uint8:
-            raise ValueError("expected matching uint8 [N, H, W, 3] images")
-        n, h, w, _ = pred_u8.shape
-        step = min(chunk_pairs(self.net, h, w), int(chunk) if chunk else n) if n else 1  # validates the size
-        out = torch.empty(n, dtype=torch.float32, device=pred_u8.device)
-        for s0 in range(0, n, max(1, step)):
-            self._chunk(pred_u8[s0:s0 + step], target_u8[s0:s0 + step], out[s0:s0 + step])
+        out = tower.score_pairs(pred_u8, target_u8, chunk, lambda h, w: chunk_pairs(self.net, h, w),
+                                lambda h, w: split_pair(self.net, h, w), self.features, self._score_tap, torch.float32)
         return out.cpu().numpy().astype(np.float64)
 
     # ------------------------------------------------------------------ training loss
-    def _bwd_weights(self):
-        """(conv1's weight as [kh][kw][4][cout] for the gather dgrad, the other convs packed for the input-gradient
-        conv, autograd.conv_dgrad's form: flipped, [cin][kh kw cout] as a stride-1 conv with pad k - 1 - p).
-        Packed on first use and owned by this instance: they go when it goes."""
-        if self._bwd is None:
-            self._bwd = pack_bwd_weights(self._raw, self.net, self.device)
-        return self._bwd
-
     def forward_acts(self, x: torch.Tensor):
         """Every activation of the prep output x [n, h, w, 4], x first, and the index of each tap in that list."""
-        acts, taps, ci = [x], [], 0
-        with ops.splitk_as((False, False)):
-            for op in self.table:
-                if op[0] == "conv":
-                    acts.append(ops.conv2d(acts[-1], self.convs[ci], act=ops.LEAKY, slope=0.0))
-                    ci += 1
-                elif op[0] == "pool":
-                    acts.append(max_pool(acts[-1], op[1], op[2]))
-                else:
-                    taps.append(len(acts) - 1)
-        return acts, taps
+        return tower.forward(self.table, self.convs, _pool, [x], keep_all=True)
 
     def features_float(self, img: torch.Tensor) -> List[torch.Tensor]:
         """The five taps of float [n, H, W, 3] images in [-1, 1]."""
@@ -272,11 +211,7 @@ class LPIPS:
         """mean_n sum_k score_k (reference model/lpips.py:85-89 with inp_range (-1, 1)) of float NHWC device images
         [N, H, W, 3] in [-1, 1], fp32 or bf16, as an fp32 device scalar. The gradient goes to pred only; the
         backbone runs in fp32 whatever the image dtype."""
-        for t in (pred, target):
-            if t.dim() != 4 or t.shape[3] != 3 or t.dtype not in (torch.float32, torch.bfloat16) or not t.is_cuda:
-                raise ValueError("LPIPS.loss: float32 / bfloat16 [N, H, W, 3] device images expected")
-        if pred.shape != target.shape or pred.shape[0] == 0:
-            raise ValueError("LPIPS.loss: prediction and target must share a non-empty shape")
+        tower.check_float_pair(pred, target, "LPIPS.loss")
         n, h, w, _ = pred.shape
         if n * image_bytes(self.net, h, w) >= MAX_TENSOR_BYTES:  # validates the size; one backbone launch per side
             raise ValueError(f"LPIPS.loss({self.net}) at {h}x{w}: {n} images' activations reach 2^31 bytes")
@@ -307,52 +242,20 @@ class _LossFn(torch.autograd.Function):
         (n, h, w, _), dtype = ctx.pred_meta
         gscore = (gout.to(torch.float32) / n).expand(n).contiguous()
         w0, packs = model._bwd_weights()
-        # forward records: (op, activation index of its input)
-        recs, i, ci, k = [], 0, 0, 0
-        for op in model.table:
-            if op[0] == "tap":
-                recs.append(("tap", i, k))
-                k += 1
-            else:
-                recs.append((op, i, ci))
-                i += 1
-                ci += op[0] == "conv"
-        d = dpred = None
         with ops.splitk_as(ctx.splitk):
-            for op, i, j in reversed(recs):
-                if op == "tap":
-                    d = layer_distance_bwd(acts[i], f1[j], model.lin[j], gscore, out=d)
-                elif d is None:
-                    continue  # nothing after the last tap
-                elif op[0] == "pool":
-                    d = max_pool_bwd(acts[i], d, op[1], op[2])
-                elif j == 0:
-                    _, _, cout, ks, s, p = op
-                    dpred = torch.empty((n, h, w, 3), dtype=dtype, device=d.device)
-                    conv_dgrad_small(d, acts[1], w0, (h, w), 4, ks, s, p, prep_bwd=True, out=dpred)
-                else:
-                    _, _, cout, ks, s, p = op
-                    z = acts[i + 1]
-                    ops.call("rdeic_act_bwd", d.data_ptr(), ops.pix_ld(d), z.data_ptr(), ops.pix_ld(z),
-                             d.numel() // cout, cout, ops.LEAKY, 0.0, d.data_ptr(), ops.pix_ld(d), 0,
-                             ops.stream_ptr())  # the ReLU mask, in place
-                    d = ops.conv2d(d, packs[j], out_hw=tuple(acts[i].shape[1:3]))  # stride 1 throughout
+            d = tower.backward(tower.backward_plan(model.table, 0), acts, packs,
+                               lambda k, x, out: layer_distance_bwd(x, f1[k], model.lin[k], gscore, out=out),
+                               lambda op, x, y, dy: max_pool_bwd(x, dy, op[1], op[2]))
+            _, _, _, ks, s, p = model.table[0]  # conv 0: the gather dgrad with its ReLU mask and the prep backward
+            dpred = torch.empty((n, h, w, 3), dtype=dtype, device=d.device)
+            conv_dgrad_small(d, acts[1], w0, (h, w), 4, ks, s, p, prep_bwd=True, out=dpred)
         return dpred, None, None
 
 
 def pack_bwd_weights(raw, net: str, device):
-    """The backward's device weights of a backbone's raw [(weight, bias)] list (LPIPS and DISTS share it): conv1 as
-    [kh][kw][4][cout], and [None] + the other convs' flipped packs, each a stride-1 conv with pad k - 1 - p."""
-    w0 = torch.nn.functional.pad(raw[0][0], (0, 0, 0, 0, 0, 1))
-    packs = [None]
-    for (w, _), (_, _, cin, cout, k, _, p) in zip(raw[1:], conv_layers(net)[1:]):
-        wd = w.to(device).contiguous()
-        wld = -(-(k * k * cout) // 64) * 64
-        packed = torch.empty((cin, wld), dtype=torch.float32, device=device)
-        ops.call("rdeic_pack_conv_weight_dgrad", wd.data_ptr(), cout, cin, k, k, packed.data_ptr(), wld, 0,
-                 ops.stream_ptr())
-        packs.append(ops.ConvParams(packed, wld, None, cin, cout, k, k, 1, k - 1 - p))
-    return w0.permute(2, 3, 1, 0).contiguous().to(device), packs
+    """tower.pack_bwd_weights of a backbone's raw [(weight, bias)] list: conv1 as [kh][kw][4][cout], and [None] +
+    the other convs' flipped packs."""
+    return tower.pack_bwd_weights(raw, conv_layers(net), device)
 
 
 def prep_float(img: torch.Tensor) -> torch.Tensor:

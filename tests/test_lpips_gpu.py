@@ -66,6 +66,46 @@ def test_max_pool_is_bit_exact(gpu, shape, k, ld_in, ld_out):
         assert torch.equal(max_pool(x.cuda(), k, 2).cpu(), want.contiguous())
 
 
+def _max_pool_rule(x, k, s):
+    """The documented rule: row-major scan of the window, strict >, a NaN wins and stays."""
+    n, h, w, c = x.shape
+    out = np.empty((n, (h - k) // s + 1, (w - k) // s + 1, c), np.float32)
+    for i, oy, ox, ch in np.ndindex(*out.shape):
+        m = x[i, oy * s, ox * s, ch]
+        for dy, dx in np.ndindex(k, k):
+            v = x[i, oy * s + dy, ox * s + dx, ch]
+            if v > m or v != v:
+                m = v
+        out[i, oy, ox, ch] = m
+    return out
+
+
+@pytest.mark.parametrize("shape,k,ld", [((1, 3, 3, 4), 3, 4), ((2, 7, 9, 6), 3, 7), ((1, 5, 5, 64), 2, 64)])
+def test_max_pool_special_values(gpu, shape, k, ld):
+    """Signed zeros, an all -inf window and a NaN before a larger element, on the vector path (c, ld % 4 == 0) and
+    the scalar one: the bits of the rule above, and of F.max_pool2d."""
+    from rdeic_amd.lpips import max_pool
+    n, h, w, c = shape
+    g = torch.Generator().manual_seed(c * 10 + k)
+    x = torch.randn((n, h, w, ld), generator=g)
+    win = x[0, :k, :k]  # the first window, one case per channel
+    win[..., 0] = -5.0
+    win[0, 1, 0], win[1, 0, 0] = -0.0, 0.0  # -0.0 comes first and stays
+    win[..., 1] = -5.0
+    win[0, 1, 1], win[1, 0, 1] = 0.0, -0.0  # +0.0 comes first and stays
+    win[..., 2] = float("-inf")
+    win[0, 1, 3], win[k - 1, k - 1, 3] = float("nan"), 100.0  # a NaN, then the window's largest element
+    want = _max_pool_rule(x[..., :c].numpy(), k, 2)
+    nan = np.isnan(want)
+    assert nan[0, 0, 0, 3] and nan.sum() == 1 and want[0, 0, 0, 2] == float("-inf")
+    assert want.view(np.int32)[0, 0, 0, 0] == np.float32(-0.0).view(np.int32) and want.view(np.int32)[0, 0, 0, 1] == 0
+    got = max_pool(x.cuda()[..., :c], k, 2).cpu().numpy()
+    ref = F.max_pool2d(x[..., :c].permute(0, 3, 1, 2), kernel_size=k, stride=2).permute(0, 2, 3, 1).contiguous().numpy()
+    for name, other in (("rule", want), ("F.max_pool2d", ref)):
+        assert got.shape == other.shape and np.array_equal(np.isnan(got), np.isnan(other)), name
+        assert np.array_equal(got.view(np.int32)[~nan], other.view(np.int32)[~nan]), name
+
+
 # ------------------------------------------------------------------ 3. layer distance
 @lru_cache(maxsize=None)
 def _taps(c, h, w):
