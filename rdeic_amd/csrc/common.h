@@ -33,6 +33,21 @@ template <> __device__ __forceinline__ float from_f32<float>(float x) { return x
 template <> __device__ __forceinline__ bf16 from_f32<bf16>(float x) { return (bf16)x; }
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
+// The bf16 GroupNorm affine (+ SiLU) rule of rdeic_groupnorm_apply's vector kernel and rdeic_groupnorm_parts_apply
+// (norm.hip): fma(a, x, b), then x * rcp(1 + e^-x) (v_rcp_f32, not the IEEE divide); the caller scales and rounds
+// to bf16. Pair form: s = (a, b) of x0's channel, then of x1's. The halo convs' in-LDS transform (halo_gn_chunk,
+// conv_halo.hip) is the same rule, eight channels at a time, and must write the same bf16 values
+// (tests/test_halo_conv_gpu.py, tests/test_gn_fused_gpu.py); it keeps its own copy because through this helper its
+// kernels compile to other code. silu_f above and gn_apply_chunk (conv_common.h) use the IEEE
+// divide: a DIFFERENT rule (the fp32-parity paths), not to be merged with this one.
+__device__ __forceinline__ void gn_fast2(float& x0, float& x1, float4 s, bool silu) {
+  x0 = __builtin_fmaf(s.x, x0, s.y);
+  x1 = __builtin_fmaf(s.z, x1, s.w);
+  if (silu) {
+    x0 *= __builtin_amdgcn_rcpf(1.0f + __expf(-x0));
+    x1 *= __builtin_amdgcn_rcpf(1.0f + __expf(-x1));
+  }
+}
 // exact-erf GELU (torch.nn.GELU / F.gelu default)
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 // GELU with erf from Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7 on erf): one rcp and one exp instead

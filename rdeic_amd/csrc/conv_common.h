@@ -532,9 +532,25 @@ __device__ unsigned long long* g_halo_stamps;
   do {                                                                                     \
     if (threadIdx.x == 0) g_halo_stamps[(long)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
+#define HALO_STAMP_IDS()  /* slots 5, 6: where the block ran (HW_ID, XCC_ID) */            \
+  do {                                                                                     \
+    if (threadIdx.x == 0) {                                                                \
+      g_halo_stamps[(long)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  \
+      g_halo_stamps[(long)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((31 << 11) | 20); \
+    }                                                                                      \
+  } while (0)
 #else
 #define HALO_STAMP(k) do {} while (0)
+#define HALO_STAMP_IDS() do {} while (0)
 #endif
+
+// XCD-aware bijective remap of a 1-D grid: blocks with equal blockIdx.x % 8 share an XCD (and its L2), so each
+// XCD gets a contiguous run of the returned ids.
+__device__ __forceinline__ int xcd_remap() {
+  const int nwg = gridDim.x, orig = blockIdx.x;
+  const int xcd = orig & 7, q = nwg >> 3, rr = nwg & 7;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+}
 
 // vmcnt(n) for a wave-uniform runtime n in [0, 7]
 __device__ __forceinline__ void wait_vm_rt(int n) {

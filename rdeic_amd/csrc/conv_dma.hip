@@ -113,10 +113,7 @@ __device__ __forceinline__ void conv_dma_body(ConvArgs a, int tiles_n, unsigned 
     a.weight += z * a.w_bs * 2;
     a.out += z * a.out_bs * (a.out_f32 ? 4 : 2);
   }
-  // XCD-aware bijective remap: blocks with equal blockIdx.x % 8 share an XCD
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q = nwg >> 3, rr = nwg & 7;
-  const int wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+  const int wgid = xcd_remap();
   int mt = wgid / tiles_n;
   const int nt = wgid - mt * tiles_n;
   int phase = 0;

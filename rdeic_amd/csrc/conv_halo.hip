@@ -12,34 +12,55 @@ namespace rdeic_conv {
 // The im2col path (conv_dma_kernel) re-stages every input element for each of the 9 taps, so a
 // GroupNorm + SiLU fused into its staging costs 9x the VALU of the element-wise pass and loses to
 // materialising silu(a x + b) in HBM (one read + one write of the activation). Here a tile is an
-// image block of TR x TC = 4 x 64 output pixels x 128 output channels; per 32-channel block the
-// (TR + 2) x (TC + 2) halo of the RAW input is DMA'd to LDS once (buffer_load ... lds, 25 x 1 KB
-// pieces, zeros outside the image from the descriptor's range check), transformed in place
-// (x * a + b, then x * rcp(1 + e^-x): exactly the bf16 values rdeic_groupnorm_apply writes; halo
-// pixels outside the image stay zero = the conv's zero padding of the normalised tensor) and then
-// read by all 9 taps. The 32-channel weight slice of each tap streams through a 3-deep ring.
+// image block of TR x TC = 4 x 64 (or 8 x 64) output pixels x 128 output channels; per 32-channel
+// block the (TR + 2) x (TC + 2) halo of the RAW input is DMA'd to LDS once (buffer_load ... lds,
+// 1 KB pieces, zeros outside the image from the descriptor's range check), transformed in place
+// (halo_gn_chunk: exactly the bf16 values rdeic_groupnorm_apply writes; halo pixels outside the image
+// stay zero = the conv's zero padding of the normalised tensor) and then read by all 9 taps. The
+// 32-channel weight slice of each tap streams through a ring of NB slots, LEAD taps ahead.
 // Per step (tap) a wave (one output row, 64 channels) issues 16 v_mfma_f32_16x16x32_bf16.
-// LDS 78 KB -> two blocks per CU, so one block's epilogue overlaps the other's main loop.
 // Swizzle: 16-byte chunk q of halo pixel / weight row s lives at slot q ^ (((s >> 2) & 1) << 1),
 // conflict-free for every ds_read_b128 lane group at any pixel offset (tap shift).
 // k order: 32-channel block major, tap minor — fixed per shape (deterministic, batch-invariant),
-// not the im2col kernels' (tap, 64-channel) order, so results differ from them by fp32 rounding.
-// The epilogue is epilogue_vec (bias / residual / GroupNorm statistics of the output) with the
-// tile's 64-pixel wave rows mapped to their image rows.
+// not the im2col kernels' (tap, 64-channel) order, so results differ from them by fp32 rounding;
+// the same in both forms, so they give bit-identical outputs.
+// The epilogue is halo_epilogue (bf16 out, no emb / activation) or epilogue_vec (bias / residual /
+// GroupNorm statistics of the output) with the tile's 64-pixel wave rows mapped to their image rows.
+//
+// Shared by the two kernels below: the geometry, the tile decode, the halo addressing, the chunk
+// transform, the tap body and the epilogue. Per kernel: who loads what, the wait / barrier schedule
+// and the ring depth, plus the few lines that only compile to the same code where they stand (the
+// 8-row kernel's in-image test and pass-0 residual DMA, the res / no-res epilogue call: DESIGN.md).
 // ============================================================================================
-namespace halo {
-constexpr int TR = HALO_TR, TC = HALO_TC;  // output rows / columns per tile (4 x 64)
-constexpr int HR = TR + 2, HC = TC + 2;   // halo rows / columns
-constexpr int HPIX = HR * HC;             // 396 halo pixels
-constexpr int NPIECE = (HPIX * 4 + 63) / 64;  // 1 KB DMA pieces per halo (25)
-constexpr int HBYTES = NPIECE * 1024;     // one halo buffer (the last piece's tail slots read zeros)
-constexpr int BN = HALO_BN, NW = 8, NT = NW * 64;  // 128 output channels per tile
-constexpr int BBYTES = BN * 64;           // one tap's 32-channel weight slice
-constexpr int NB = 3;                     // weight ring depth
-constexpr int AB_MAX = HALO_AB_MAX;       // input channels whose GroupNorm affine fits the LDS table
-constexpr int LDS = 2 * HBYTES + NB * BBYTES + AB_MAX * 8;
-static_assert(LDS <= 80 * 1024, "two blocks per CU");
-static_assert((TR * TC / 2) * (BN + 4) * 4 <= LDS, "epilogue parking (two passes)");
+template <int TR_, int NW_, int NB_, int LEAD_>
+struct HaloGeom {
+  static constexpr int TR = TR_, TC = HALO_TC;      // output rows / columns per tile
+  static constexpr int HR = TR + 2, HC = TC + 2;    // halo rows / columns
+  static constexpr int HPIX = HR * HC;              // halo pixels (396 / 660)
+  static constexpr int NPIECE = (HPIX * 4 + 63) / 64;  // 1 KB DMA pieces per halo (25 / 42)
+  static constexpr int HBYTES = NPIECE * 1024;      // one halo buffer (the last piece's tail slots read zeros)
+  static constexpr int BN = HALO_BN, NW = NW_, NT = NW * 64;  // 128 output channels per tile
+  static constexpr int BBYTES = BN * 64;            // one tap's 32-channel weight slice
+  static constexpr int NB = NB_, LEAD = LEAD_;      // weight ring: NB slots, slice u + LEAD issued at tap u
+  static constexpr int AB_MAX = HALO_AB_MAX;        // input channels whose GroupNorm affine fits the LDS table
+  static constexpr int TABLE = 2 * HBYTES + NB * BBYTES;  // halo double buffer + ring; the (a, b) table follows
+  static constexpr int LDS = TABLE + AB_MAX * 8;
+  // Epilogue LDS plan (halo_epilogue: four passes of NW x 8 tile rows, one 16-row fragment per wave row): a parked
+  // pass (fp32, BN + 4 per row) and pass 0's residual rows, DMA'd during the main loop's last taps into the halo
+  // buffer the last channel block does not read, so the layout depends on the parity of the channel-block count.
+  static constexpr int PK_BYTES = NW * 8 * (BN + 4) * 4, RES_BYTES = NW * 8 * BN * 2;
+  static_assert(NW == 2 * TR, "a wave = (output row, 64-channel half)");
+  static_assert(LDS * (16 / NW) <= 160 * 1024, "16 waves of blocks per CU");
+  static_assert(NB >= LEAD + 1, "a slot is reused only after every wave passed the barrier of its last reader");
+  static_assert((TR * TC / 2) * (BN + 4) * 4 <= LDS, "epilogue_vec parking (two passes)");
+  static_assert(RES_BYTES <= HBYTES && HBYTES + PK_BYTES + RES_BYTES <= TABLE, "epilogue plan, either parity");
+  static __device__ __forceinline__ int res_off(int parity) { return parity ? HBYTES : 0; }  // pass 0's residual
+  static __device__ __forceinline__ int park_off(int parity) { return parity ? HBYTES + RES_BYTES : HBYTES; }
+};
+// 4-row form: LDS 78 KB -> two blocks per CU, so one block's epilogue overlaps the other's main loop
+using Halo4 = HaloGeom<HALO_TR, 8, 3, 2>;
+using Halo8 = HaloGeom<HALO8_TR, 16, 8, 6>;
+
 __device__ __forceinline__ int sw(int s) { return ((s >> 2) & 1) << 1; }
 
 struct Rows {  // tile row r (wave row r / 64, column r % 64) -> output pixel
@@ -47,36 +68,94 @@ struct Rows {  // tile row r (wave row r / 64, column r % 64) -> output pixel
   __device__ __forceinline__ int operator()(int r) const { return base + (r >> 6) * W + (r & 63); }
 };
 
-// Epilogue LDS plan (four passes of 64 tile rows: one 16-row fragment per wave row): a parked pass
-// (64 x (BN + 4) fp32) and two 16 KB residual buffers. Pass 0's residual is DMA'd during the main loop's
-// last taps into the halo buffer the last channel block does not read, so the layout depends on the
-// parity of the channel-block count.
-constexpr int PK_BYTES = 64 * (BN + 4) * 4;  // 33,792
-constexpr int RES_BYTES = 64 * BN * 2;       // 16,384: 64 pixels x 128 bf16
-constexpr int RING_END = 2 * HBYTES + NB * BBYTES;
-static_assert(HBYTES + PK_BYTES + RES_BYTES <= RING_END, "epilogue plan, even channel blocks");
-static_assert(HBYTES + RES_BYTES + PK_BYTES <= RING_END, "epilogue plan, odd channel blocks");
-static_assert(RES_BYTES <= HBYTES, "pass-0 residual in the free halo buffer");
-__device__ __forceinline__ int res_off(int parity, int p) {  // residual buffer of pass p
-  return ((p & 1) == 0) ? (parity ? HBYTES : 0) : (parity ? 0 : HBYTES + PK_BYTES);
+// The block's tile: XCD-aware remap (an XCD owns a contiguous run of tile ids, the N tiles of one image block
+// adjacent: they share its halo through L2), then (image, first output row / column, first output channel).
+// H, PT: the input rows of this launch's view and the zero rows above them (a row band carries its neighbour
+// rows: PT = 0 above an interior band, 1 = the image's zero padding; one launch over whole images has H = a.ho, PT = 1).
+struct HaloTile { int img, oy0, ox0, n0, H, PT; };
+template <class G>
+__device__ __forceinline__ HaloTile halo_tile(const ConvArgs& a, int tiles_x, int tiles_y) {
+  const int tn = a.cout / G::BN;
+  const int wgid = xcd_remap();
+  const int nt = wgid % tn;
+  int sp = wgid / tn;
+  const int tx = sp % tiles_x;
+  sp /= tiles_x;
+  const int ty = sp % tiles_y, img = sp / tiles_y;
+  return HaloTile{img, ty * G::TR, tx * G::TC, nt * G::BN, a.h, a.pad_t};
 }
-__device__ __forceinline__ int park_off(int parity) { return parity ? HBYTES + RES_BYTES : HBYTES; }
-}  // namespace halo
 
-// Pass 0's residual rows (NW x 8 pixels x 128 channels) by LDS-DMA, issued by the 4-row kernel during its last
-// taps: this wave's pieces q = wave, wave + NW; lane i of piece q brings pass row 4q + i / 16 (wave row (4q + i / 16) / 16, pixel
-// p * 16 + (4q + i / 16) % 16 of it), channels n0 + 8 (i % 16) .. + 7. Offsets are recomputed at each use
-// (not kept live).
-template <int NW>
+// Halo slot sl of tile t -> the DMA byte offset of its 16-byte chunk ph at its swizzled place, or kOOB (reads
+// zeros) for the slots past the halo and the pixels outside the image.
+template <class G>
+__device__ __forceinline__ unsigned halo_voff(const ConvArgs& a, const HaloTile& t, int sl, int ph) {
+  unsigned vo = kOOB;
+  if (sl < G::HPIX) {
+    const int hr = sl / G::HC, hc = sl - (sl / G::HC) * G::HC;
+    const int iy = t.oy0 - t.PT + hr, ix = t.ox0 - 1 + hc;
+    if ((unsigned)iy < (unsigned)t.H && (unsigned)ix < (unsigned)a.w)
+      vo = (unsigned)((t.img * t.H + iy) * a.w + ix) * (unsigned)(a.ld0 * 2) + (unsigned)((ph ^ sw(sl)) * 16);
+  }
+  return vo;
+}
+
+// The GroupNorm (GN = 1) + SiLU (GN = 2) of one 16-byte chunk v of a halo; ab: the (a, b) of its 8 channels.
+// The rule of gn_fast2 (common.h), eight channels at a time: fma(x, a, b), x * rcp(1 + e^-x), round to bf16.
+template <int GN>
+__device__ __forceinline__ bf16x8 halo_gn_chunk(bf16x8 v, const float* ab) {
+  const float4* ab4 = reinterpret_cast<const float4*>(ab);
+  const float4 t0 = ab4[0], t1 = ab4[1], t2 = ab4[2], t3 = ab4[3];
+  const float av[8] = {t0.x, t0.z, t1.x, t1.z, t2.x, t2.z, t3.x, t3.z};
+  const float bv[8] = {t0.y, t0.w, t1.y, t1.w, t2.y, t2.w, t3.y, t3.w};
+  bf16x8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float x = __builtin_fmaf((float)v[e], av[e], bv[e]);
+    if constexpr (GN == 2) x *= __builtin_amdgcn_rcpf(1.0f + __expf(-x));
+    o[e] = (bf16)x;
+  }
+  return o;
+}
+
+// One tap t of a channel block: the wave's 64 x 64 tile += halo rows (hb) x the tap's weight slice (bb: the
+// lane's row of it). A fragment i reads halo slots s0 + 16 i + lr: adding 16 leaves bits 0..3 (and so the
+// swizzle) unchanged, so one lane address per tap serves all four fragments (immediate offsets).
+template <int HC>
+__device__ __forceinline__ void halo_tap(f32x4 (&acc)[4][4], const char* hb, const char* bb, int t, int wm, int lr,
+                                         int lq) {
+  const int ky = t / 3, kx = t - (t / 3) * 3;
+  bf16x8 bfv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bfv[j] = *reinterpret_cast<const bf16x8*>(bb + j * 16 * 64);
+  // per-tap lane address, recomputed each tap from a laundered base (the compiler would otherwise
+  // hoist all 9 taps' addresses out of the channel-block loop and spill)
+  int lb = wm * HC + lr;
+  asm volatile("" : "+v"(lb));
+  const int sl = lb + ky * HC + kx;
+  const char* ab = hb + sl * 64 + ((lq ^ sw(sl)) << 4);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const bf16x8 af = *reinterpret_cast<const bf16x8*>(ab + i * 1024);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfv[j], acc[i][j], 0, 0, 0);
+  }
+}
+
+// Pass 0's residual rows (NW x 8 pixels x 128 channels) by LDS-DMA, issued during the main loop's last taps by
+// eight waves w = 0..7: pieces q = w + 8 k, k < NK (NW x 8 / 4 pieces in all); lane i of piece q brings pass row
+// 4q + i / 16 (wave row (4q + i / 16) / 16, pixel (4q + i / 16) % 16 of it), channels n0 + 8 (i % 16) .. + 7.
+// Offsets are recomputed here (not kept live). The 8-row kernel writes the same addressing out at its call site:
+// through this helper its code changes.
+template <int NK>
 __device__ __forceinline__ void halo_res_dma(__amdgpu_buffer_rsrc_t rsr, char* dst, int base, int W, int res_ld,
-                                             int n0, int wave, int lane, int p) {
+                                             int n0, int w, int lane) {
   int l = lane;
   asm volatile("" : "+v"(l));  // keep the offsets here, not hoisted into the main loop's live set
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int pr = 4 * (wave + NW * k) + (l >> 4);
+  for (int k = 0; k < NK; ++k) {
+    const int q = w + 8 * k, pr = 4 * q + (l >> 4);
     const unsigned vo = (unsigned)(base + (pr >> 4) * W + (pr & 15)) * (unsigned)(res_ld * 2) + (unsigned)((l & 15) * 16);
-    dma16(rsr, dst + (wave + NW * k) * 1024, vo, p * 16 * res_ld * 2 + n0 * 2);
+    dma16(rsr, dst + q * 1024, vo, n0 * 2);
   }
 }
 
@@ -85,15 +164,15 @@ __device__ __forceinline__ void halo_res_dma(__amdgpu_buffer_rsrc_t rsr, char* d
 // tile rows). Per pass: the accumulators of fragment row p are parked in LDS (park). Pass 0's residual rows
 // are in LDS at r0 (LDS-DMA'd by the caller during its last taps); passes 1-3 buffer-load theirs into
 // registers one pass ahead (rbuf), so only LDS-only barriers separate the passes (an LDS-DMA here would make
-// the compiler drain vmcnt(0) before the next LDS read; r1 is not used). Each thread keeps the bias of its
+// the compiler drain vmcnt(0) before the next LDS read). Each thread keeps the bias of its
 // 8 channels in registers and handles 2 chunks (16-byte LDS reads, residual, one 16-byte store each).
 // Arithmetic and rounding are epilogue_vec's, so outputs are bit-identical to it. Fused GroupNorm
 // statistics (a.gn_part) keep the canonical order: pass p is 16-row group p of every 64-row block (one wave
 // row), summed by a column scan of the stored values, and ((g0 + g1) + g2) + g3 at the end.
 template <int NW, bool RES>
 __device__ __forceinline__ void halo_epilogue(const f32x4 (&acc)[4][4], const ConvArgs& a, int n0, int wm, int wn,
-                                              int tid, char* lds, int base, int W, int park, int r0, int r1,
-                                              __amdgpu_buffer_rsrc_t rsr, int wave) {
+                                              int tid, char* lds, int base, int W, int park, int r0,
+                                              __amdgpu_buffer_rsrc_t rsr) {
   constexpr int BN = 128, SDW = BN + 4, NT = NW * 64;
   // laundered: every address below is derived after the main loop (hoisted, they would sit in the
   // 128-VGPR main loop's live set and spill)
@@ -115,9 +194,7 @@ __device__ __forceinline__ void halo_epilogue(const f32x4 (&acc)[4][4], const Co
   }
   float sg[4], qg[4];
   // LDS-only barriers (__syncthreads() would also drain vmcnt(0): the previous pass's output stores and the
-  // next pass's residual loads). The residual of pass 0 is in LDS (r0, LDS-DMA'd by the caller during its
-  // last taps); passes 1-3 load theirs into registers one pass ahead (an LDS-DMA here would make the compiler
-  // drain vmcnt(0) before the next LDS read, i.e. wait out the prefetch at once).
+  // next pass's residual loads).
   auto bar = []() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   auto res_rows = [&](int p, uint4 (&dst)[2]) {
 #pragma unroll
@@ -192,39 +269,24 @@ __device__ __forceinline__ void halo_epilogue(const f32x4 (&acc)[4][4], const Co
     if (tid == 0 && base == 0 && n0 == 0) reinterpret_cast<int*>(a.gn_part)[0] = 64;  // rows per partial
   }
 }
-
-// GN: 0 plain conv, 1 GroupNorm affine on the input, 2 affine + SiLU (compile-time: no per-element branch);
-// FE: the fast epilogue (halo_epilogue: bf16 out, no emb / activation), else epilogue_vec
+// The 4-row kernel. GN: 0 plain conv, 1 GroupNorm affine on the input, 2 affine + SiLU (compile-time: no
+// per-element branch); FE: the fast epilogue (halo_epilogue: bf16 out, no emb / activation), else epilogue_vec.
+// Every wave loads its share of both streams (3-deep weight ring, 2 taps ahead) and transforms the halo chunks
+// its own DMA pieces brought in.
 template <int GN, bool FE>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv3x3_halo_kernel(ConvArgs a, int tiles_x, int tiles_y, unsigned bytes0,
                                                                unsigned bytesw) {
-  using namespace halo;
+  using G = Halo4;
+  constexpr int HBYTES = G::HBYTES, BBYTES = G::BBYTES, NB = G::NB, NPIECE = G::NPIECE;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char* const hbuf = lds;
   char* const bbuf = lds + 2 * HBYTES;
-  float* const abl = reinterpret_cast<float*>(lds + 2 * HBYTES + NB * BBYTES);
+  float* const abl = reinterpret_cast<float*>(lds + G::TABLE);
   HALO_STAMP(0);
-#ifdef RDEIC_HALO_STAMPS
-  if (threadIdx.x == 0) {
-    g_halo_stamps[(long)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-    g_halo_stamps[(long)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-  }
-#endif
-  const int tn = a.cout / BN;
-  // XCD-aware bijective remap (as conv_dma_body): an XCD owns a contiguous run of tile ids, the N
-  // tiles of one image block adjacent (they share its halo through L2)
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, rr = nwg & 7;
-  const int wgid = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (orig >> 3);
-  const int nt = wgid % tn;
-  int sp = wgid / tn;
-  const int tx = sp % tiles_x;
-  sp /= tiles_x;
-  const int ty = sp % tiles_y, img = sp / tiles_y;
-  const int oy0 = ty * TR, ox0 = tx * TC, n0 = nt * BN;
-  // input rows H of this launch's view (a row band carries its neighbour rows: PT = 0 above an interior band, 1 =
-  // the image's zero padding) and output rows HO; one launch over whole images has H = HO, PT = 1
-  const int H = a.h, HO = a.ho, PT = a.pad_t, W = a.w, cin = a.c0;
+  HALO_STAMP_IDS();
+  const HaloTile tl = halo_tile<G>(a, tiles_x, tiles_y);
+  const int img = tl.img, oy0 = tl.oy0, ox0 = tl.ox0, n0 = tl.n0;
+  const int HO = a.ho, W = a.w, cin = a.c0;
   const int ncb = cin >> 5, U = ncb * 9;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -240,18 +302,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int p = (wave + 8 * k < NPIECE) ? wave + 8 * k : wave + 16;
-    const int sl = p * 16 + (lane >> 2), ph = lane & 3;
     hpo[k] = p * 1024;
-    hvo[k] = kOOB;
-    if (sl < HPIX) {
-      const int hr = sl / HC, hc = sl - (sl / HC) * HC;
-      const int iy = oy0 - PT + hr, ix = ox0 - 1 + hc;
-      if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-        hvo[k] = (unsigned)((img * H + iy) * W + ix) * (unsigned)(a.ld0 * 2) + (unsigned)((ph ^ sw(sl)) * 16);
-    }
+    hvo[k] = halo_voff<G>(a, tl, p * 16 + (lane >> 2), lane & 3);
   }
-  // residual pieces of the epilogue (halo_epilogue): this wave's pieces q = wave, wave + 8 of every pass;
-  // lane i of piece q brings pass row 4q + i / 16 (wave row (4q + i / 16) / 16), chunk i % 16
+  // residual pieces of the epilogue (halo_epilogue): this wave's pieces q = wave, wave + 8 of pass 0
   const bool res_dma = FE && a.res != nullptr;
   const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(res_dma ? a.res : a.in0), (short)0, res_dma ? (int)((long)(img * HO + HO) * W * a.res_ld * 2) : 0, 0x00020000);
@@ -288,21 +342,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // piece k of this wave's halo pieces (one 16-byte chunk per lane), transformed in place
   auto transform_piece = [&](int cb, int k) {
     if (!(hinfo & (1u << k))) return;
-    char* hb = hbuf + (cb & 1) * HBYTES + lane * 16 + hpo[k];
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(hb);
+    bf16x8* hb = reinterpret_cast<bf16x8*>(hbuf + (cb & 1) * HBYTES + lane * 16 + hpo[k]);
+    const bf16x8 v = *hb;
     const int ch = (hinfo >> (4 + 2 * k)) & 3;
-    const float4* ab4 = reinterpret_cast<const float4*>(abl + (cb * 32 + ch * 8) * 2);
-    const float4 t0 = ab4[0], t1 = ab4[1], t2 = ab4[2], t3 = ab4[3];  // (a, b) of the chunk's 8 channels
-    const float av[8] = {t0.x, t0.z, t1.x, t1.z, t2.x, t2.z, t3.x, t3.z};
-    const float bv[8] = {t0.y, t0.w, t1.y, t1.w, t2.y, t2.w, t3.y, t3.w};
-    bf16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float x = __builtin_fmaf((float)v[e], av[e], bv[e]);
-      if constexpr (GN == 2) x *= __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-      o[e] = (bf16)x;
-    }
-    *reinterpret_cast<bf16x8*>(hb) = o;
+    *hb = halo_gn_chunk<GN>(v, abl + (cb * 32 + ch * 8) * 2);
   };
   auto transform = [&](int cb) {
 #pragma unroll
@@ -337,8 +380,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   HALO_STAMP(1);
   const int lr = lane & 15, lq = lane >> 4;
   const int bsw = (lq ^ sw(lr)) * 16;  // weight rows n = 64 wn + 16 j + lr share sw(lr)
-  // A fragment i of a tap reads halo slots s0 + 16 i + lr: adding 16 leaves bits 0..3 (and so the
-  // swizzle) unchanged, so one lane address per tap serves all four fragments (immediate offsets)
   // taps unrolled: ring slot (u % 3 = t % 3, 9 taps per block), filter offset, waits and the next
   // loads are compile-time per tap; the only runtime branch is "is there a next channel block"
   for (int cb = 0; cb < ncb; ++cb) {
@@ -365,24 +406,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
       if (t == 0 && more) issue_halo(cb + 1);
       if (t == 7 && !more && res_dma)  // pass 0's residual rows into the halo buffer the last block does not read
-        halo_res_dma<NW>(rsr, lds + halo::res_off(parity, 0), (img * HO + oy0) * W + ox0, W, a.res_ld, n0, wave, lane, 0);
-      const char* bb = bbuf + (t % NB) * BBYTES + (wn * 64 + lr) * 64 + bsw;
-      const int ky = t / 3, kx = t - (t / 3) * 3;
-      bf16x8 bfv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bfv[j] = *reinterpret_cast<const bf16x8*>(bb + j * 16 * 64);
-      // per-tap lane address, recomputed each tap from a laundered base (the compiler would otherwise
-      // hoist all 9 taps' addresses out of the channel-block loop and spill)
-      int lb = wm * HC + lr;
-      asm volatile("" : "+v"(lb));
-      const int sl = lb + ky * HC + kx;
-      const char* ab = hb + sl * 64 + ((lq ^ sw(sl)) << 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bf16x8 af = *reinterpret_cast<const bf16x8*>(ab + i * 1024);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfv[j], acc[i][j], 0, 0, 0);
-      }
+        halo_res_dma<2>(rsr, lds + G::res_off(parity), (img * HO + oy0) * W + ox0, W, a.res_ld, n0, wave, lane);
+      halo_tap<G::HC>(acc, hb, bbuf + (t % NB) * BBYTES + (wn * 64 + lr) * 64 + bsw, t, wm, lr, lq);
       // the next block's halo (own pieces landed at tap 2's wait) is transformed one piece per tap over
       // taps 2..5, AFTER this tap's MFMAs are issued, so its VALU runs beside the matrix pipe instead of
       // delaying the next barrier; the block reads it from its tap 0 on (several barriers later)
@@ -396,14 +421,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   HALO_STAMP(2);
   if constexpr (FE) {
     if (a.res)
-      halo_epilogue<NW, true>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, park_off(parity),
-                              res_off(parity, 0), res_off(parity, 1), rsr, wave);
+      halo_epilogue<G::NW, true>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, G::park_off(parity),
+                                 G::res_off(parity), rsr);
     else
-      halo_epilogue<NW, false>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, park_off(parity),
-                               res_off(parity, 0), res_off(parity, 1), rsr, wave);
+      halo_epilogue<G::NW, false>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, G::park_off(parity),
+                                  G::res_off(parity), rsr);
   } else {
-    epilogue_vec<TR * TC, BN, 4, 2, NT, 2, Rows, false>(acc, a, 0, n0, wm, wn, lane, tid, lds,
-                                                        Rows{(img * HO + oy0) * W + ox0, W});
+    epilogue_vec<G::TR * G::TC, G::BN, 4, 2, G::NT, 2, Rows, false>(acc, a, 0, n0, wm, wn, lane, tid, lds,
+                                                                    Rows{(img * HO + oy0) * W + ox0, W});
   }
   HALO_STAMP(3);
 }
@@ -417,61 +442,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // 2 taps ahead, left the main loop waiting on ~1.1 us LDS-DMA landings, tools/halo_stamps.hip, r04).
 // Roles are split so every wave's vmcnt counts only its own stream: waves 0..7 stream the weight slices
 // (1 KB = 16 rows each), waves 8..15 the halo pieces (6 each, duplicates for the 42 pieces) and the
-// GroupNorm table, and transform the pieces they loaded (affine + SiLU in place). Same MFMA order as
+// GroupNorm table; all 16 waves transform (affine + SiLU in place). Same MFMA order as
 // the 4-row kernel (channel block major, tap minor), so both give bit-identical outputs.
 // ============================================================================================
-namespace halo8 {
-constexpr int TR = HALO8_TR, TC = HALO_TC;  // 8 x 64
-constexpr int HR = TR + 2, HC = TC + 2;            // 10 x 66 halo pixels
-constexpr int HPIX = HR * HC;                      // 660
-constexpr int NPIECE = (HPIX * 4 + 63) / 64;       // 42 pieces of 1 KB
-constexpr int HBYTES = NPIECE * 1024;              // 43,008
-constexpr int BN = 128, NW = 16, NT = NW * 64;
-constexpr int BBYTES = BN * 64;                    // one tap's 32-channel weight slice
-constexpr int NB = 8, LEAD = 6;                    // weight ring: slice u + LEAD issued at tap u
-constexpr int PPW = 6;                             // halo pieces per halo wave (8 waves x 6 >= 42)
-constexpr int AB_MAX = 512;
-constexpr int TABLE = 2 * HBYTES + NB * BBYTES;    // 151,552
-constexpr int LDS = TABLE + AB_MAX * 8;            // 155,648
-static_assert(LDS <= 160 * 1024, "one block per CU");
-static_assert(NB >= LEAD + 1, "a slot is reused only after every wave passed the barrier of its last reader");
-// epilogue (halo_epilogue<16>): park 128 rows x 132 fp32, two 32 KB residual pass buffers; pass 0's
-// residual lands in the halo buffer the last channel block does not read (index = ncb & 1)
-constexpr int PK = 128 * (BN + 4) * 4, RB = 128 * BN * 2;
-static_assert(RB <= HBYTES && HBYTES + RB + PK <= LDS && HBYTES + PK + RB <= LDS, "epilogue plan");
-__device__ __forceinline__ int res_off(int f, int p) { return ((p & 1) == 0) ? (f ? HBYTES : 0) : (f ? 0 : HBYTES + PK); }
-__device__ __forceinline__ int park_off(int f) { return f ? HBYTES + RB : HBYTES; }
-__device__ __forceinline__ int sw(int s) { return ((s >> 2) & 1) << 1; }
-}  // namespace halo8
-
 template <int GN>
 __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int tiles_x, int tiles_y, unsigned bytes0,
                                                             unsigned bytesw) {
-  using namespace halo8;
+  using G = Halo8;
+  constexpr int HBYTES = G::HBYTES, BBYTES = G::BBYTES, NB = G::NB, LEAD = G::LEAD, NPIECE = G::NPIECE;
+  constexpr int PPW = 6;  // halo pieces per halo wave (8 waves x 6 >= 42)
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char* const hbuf = lds;
   char* const bbuf = lds + 2 * HBYTES;
-  float* const abl = reinterpret_cast<float*>(lds + TABLE);
+  float* const abl = reinterpret_cast<float*>(lds + G::TABLE);
   HALO_STAMP(0);
-#ifdef RDEIC_HALO_STAMPS
-  if (threadIdx.x == 0) {
-    g_halo_stamps[(long)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-    g_halo_stamps[(long)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-  }
-#endif
-  const int tn = a.cout / BN;
-  const int nwg = gridDim.x, orig = blockIdx.x;  // XCD-aware bijective remap (as conv3x3_halo_kernel)
-  const int xcd = orig & 7, q8 = nwg >> 3, rr = nwg & 7;
-  const int wgid = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (orig >> 3);
-  const int nt = wgid % tn;
-  int sp = wgid / tn;
-  const int tx = sp % tiles_x;
-  sp /= tiles_x;
-  const int ty = sp % tiles_y, img = sp / tiles_y;
-  const int oy0 = ty * TR, ox0 = tx * TC, n0 = nt * BN;
-  // input rows H of this launch's view (a row band carries its neighbour rows: PT = 0 above an interior band, 1 =
-  // the image's zero padding) and output rows HO; one launch over whole images has H = HO, PT = 1
-  const int H = a.h, HO = a.ho, PT = a.pad_t, W = a.w, cin = a.c0;
+  HALO_STAMP_IDS();
+  const HaloTile tl = halo_tile<G>(a, tiles_x, tiles_y);
+  const int img = tl.img, oy0 = tl.oy0, ox0 = tl.ox0, n0 = tl.n0;
+  const int HO = a.ho, W = a.w, cin = a.c0;
   const int ncb = cin >> 5, U = ncb * 9;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -490,19 +478,6 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
   // A piece's source offset (or out-of-image zeros) is recomputed at each issue from a laundered lane id
   // (six live offsets would push the 128-VGPR loop into scratch).
   auto hpiece = [&](int k) { return hw + 8 * k < NPIECE ? hw + 8 * k : hw + 32; };  // wave-uniform
-  auto halo_voff = [&](int k, int ln) {
-    const int p = hpiece(k);
-    const int sl = p * 16 + (ln >> 2), ph = ln & 3;
-    unsigned vo = kOOB;
-    if (sl < HPIX) {
-      const int hr = sl / HC, hc = sl - (sl / HC) * HC;
-      const int iy = oy0 - PT + hr, ix = ox0 - 1 + hc;
-      if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-        vo = (unsigned)((img * H + iy) * W + ix) * (unsigned)(a.ld0 * 2) + (unsigned)((ph ^ sw(sl)) * 16);
-    }
-    return vo;
-  };
-  auto hpo = [&](int k) { return hpiece(k) * 1024; };
   // The GroupNorm transform is balanced over all 16 waves: wave w transforms pieces w + 16 k (k < 3,
   // < 42) whoever loaded them (r04: -3.5% against transforming by the loader). tinfo: per k a valid bit
   // (bit k: a real piece inside the image) and the lane's logical channel chunk (bits 8 + 2k).
@@ -512,10 +487,10 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
     const int p = wave + 16 * k;
     const int sl = p * 16 + (lane >> 2), ph = lane & 3;
     bool in = false;
-    if (p < NPIECE && sl < HPIX) {
-      const int hr = sl / HC, hc = sl - (sl / HC) * HC;
-      const int iy = oy0 - PT + hr, ix = ox0 - 1 + hc;
-      in = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+    if (p < NPIECE && sl < G::HPIX) {
+      const int hr = sl / G::HC, hc = sl - (sl / G::HC) * G::HC;
+      const int iy = oy0 - tl.PT + hr, ix = ox0 - 1 + hc;
+      in = (unsigned)iy < (unsigned)tl.H && (unsigned)ix < (unsigned)W;
     }
     if (in) tinfo |= 1u << k;
     tinfo |= (unsigned)(ph ^ sw(sl)) << (8 + 2 * k);
@@ -526,7 +501,9 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
     int ln = lane;
     asm volatile("" : "+v"(ln));
 #pragma unroll
-    for (int k = k0; k < k1; ++k) dma16(rs0, dst + hpo(k), halo_voff(k, ln), cb * 64);
+    for (int k = k0; k < k1; ++k) {
+      dma16(rs0, dst + hpiece(k) * 1024, halo_voff<G>(a, tl, hpiece(k) * 16 + (ln >> 2), ln & 3), cb * 64);
+    }
   };
   // weight waves: rows n = 16 wave + lane / 4, chunk lane % 4 of every tap slice
   unsigned bvo = kOOB;
@@ -547,21 +524,10 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
     int ln = lane;
     asm volatile("" : "+v"(info), "+v"(ln));
     if (!(info & (1u << k))) return;
-    char* pc = hbuf + (cb & 1) * HBYTES + ln * 16 + (wave + 16 * k) * 1024;
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(pc);
+    bf16x8* pc = reinterpret_cast<bf16x8*>(hbuf + (cb & 1) * HBYTES + ln * 16 + (wave + 16 * k) * 1024);
+    const bf16x8 v = *pc;
     const int ch = (info >> (8 + 2 * k)) & 3;
-    const float4* ab4 = reinterpret_cast<const float4*>(abl + (cb * 32 + ch * 8) * 2);
-    const float4 t0 = ab4[0], t1 = ab4[1], t2 = ab4[2], t3 = ab4[3];
-    const float av[8] = {t0.x, t0.z, t1.x, t1.z, t2.x, t2.z, t3.x, t3.z};
-    const float bv[8] = {t0.y, t0.w, t1.y, t1.w, t2.y, t2.w, t3.y, t3.w};
-    bf16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float x = __builtin_fmaf((float)v[e], av[e], bv[e]);
-      if constexpr (GN == 2) x *= __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-      o[e] = (bf16)x;
-    }
-    *reinterpret_cast<bf16x8*>(pc) = o;
+    *pc = halo_gn_chunk<GN>(v, abl + (cb * 32 + ch * 8) * 2);
   };
 
   f32x4 acc[4][4];
@@ -637,24 +603,10 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
         for (int k = 0; k < 4; ++k) {
           const int q = hw + 8 * k, pr = 4 * q + (l >> 4);
           const unsigned vo = (unsigned)(base + (pr >> 4) * W + (pr & 15)) * (unsigned)(a.res_ld * 2) + (unsigned)((l & 15) * 16);
-          dma16(rsr, lds + res_off(f, 0) + q * 1024, vo, n0 * 2);
+          dma16(rsr, lds + G::res_off(f) + q * 1024, vo, n0 * 2);
         }
       }
-      const char* bb = bbuf + (u % NB) * BBYTES + (wn * 64 + lr) * 64 + bsw;
-      const int ky = t / 3, kx = t - (t / 3) * 3;
-      bf16x8 bfv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bfv[j] = *reinterpret_cast<const bf16x8*>(bb + j * 16 * 64);
-      int lb = wm * HC + lr;
-      asm volatile("" : "+v"(lb));
-      const int sl = lb + ky * HC + kx;
-      const char* ab = hb + sl * 64 + ((lq ^ sw(sl)) << 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bf16x8 af = *reinterpret_cast<const bf16x8*>(ab + i * 1024);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfv[j], acc[i][j], 0, 0, 0);
-      }
+      halo_tap<G::HC>(acc, hb, bbuf + (u % NB) * BBYTES + (wn * 64 + lr) * 64 + bsw, t, wm, lr, lq);
       // the next block's transform: pieces wave + 16 k, k = 0..2, by every wave at taps 4..6 (the loaders'
       // tap-4 wait and barrier made them visible), after this tap's MFMAs in program order
       if constexpr (GN != 0)
@@ -666,11 +618,9 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
   }
   HALO_STAMP(2);
   if (a.res)
-    halo_epilogue<NW, true>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, park_off(f), res_off(f, 0),
-                            res_off(f, 1), rsr, wave);
+    halo_epilogue<G::NW, true>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, G::park_off(f), G::res_off(f), rsr);
   else
-    halo_epilogue<NW, false>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, park_off(f), res_off(f, 0),
-                             res_off(f, 1), rsr, wave);
+    halo_epilogue<G::NW, false>(acc, a, n0, wm, wn, tid, lds, (img * HO + oy0) * W + ox0, W, G::park_off(f), G::res_off(f), rsr);
   HALO_STAMP(3);
 }
 
@@ -679,10 +629,20 @@ __global__ __launch_bounds__(1024) void conv3x3_halo8_kernel(ConvArgs a, int til
 // an interior band carries its neighbour rows, only the image's own borders read the zero padding) and of the
 // output / residual. Bit-identical to one launch.
 int launch_halo(const rdeic_conv_desc* d, const Plan& p, ConvArgs a, hipStream_t s, bool* fused) {
-  using namespace halo;
+  using Kernel = void (*)(ConvArgs, int, int, unsigned, unsigned);
+  struct Form { int tr, nt, lds; Kernel k[3][2]; };  // [GN mode][FE]
+  static const Form forms[2] = {
+      {Halo4::TR, Halo4::NT, Halo4::LDS,
+       {{conv3x3_halo_kernel<0, false>, conv3x3_halo_kernel<0, true>},
+        {conv3x3_halo_kernel<1, false>, conv3x3_halo_kernel<1, true>},
+        {conv3x3_halo_kernel<2, false>, conv3x3_halo_kernel<2, true>}}},
+      {Halo8::TR, Halo8::NT, Halo8::LDS,  // halo8_form implies FE: one kernel per GN mode
+       {{conv3x3_halo8_kernel<0>, conv3x3_halo8_kernel<0>},
+        {conv3x3_halo8_kernel<1>, conv3x3_halo8_kernel<1>},
+        {conv3x3_halo8_kernel<2>, conv3x3_halo8_kernel<2>}}}};
   const long ipix = (long)d->h * d->w;
   const bool fe = !a.out_f32 && !a.emb && a.act == 0;
-  const bool h8 = halo8_form(d);  // the 8-row, one-block-per-CU form
+  const Form& f = forms[halo8_form(d)];  // the 8-row, one-block-per-CU form, or the 4-row one
   const bool stats = a.gn_part != nullptr && d->gn_hw == ipix;
   if (fused) *fused = stats;
   if (!stats) a.gn_part = nullptr;
@@ -692,25 +652,9 @@ int launch_halo(const rdeic_conv_desc* d, const Plan& p, ConvArgs a, hipStream_t
     const unsigned bw = (unsigned)((long)d->cout * d->wld * 2);
     rdeic_count_launch(RDEIC_COUNT_HALO_CONV);
     const int gm = e.gn_ab ? (e.gn_silu ? 2 : 1) : 0;
-    if (h8) {
-      const int tx8 = d->w / halo8::TC, ty8 = e.ho / halo8::TR;
-      const dim3 g8((unsigned)((long)e.n * ty8 * tx8 * (d->cout / halo8::BN))), b8(halo8::NT);
-      if (gm == 2) hipLaunchKernelGGL((conv3x3_halo8_kernel<2>), g8, b8, halo8::LDS, s, e, tx8, ty8, b0, bw);
-      else if (gm == 1) hipLaunchKernelGGL((conv3x3_halo8_kernel<1>), g8, b8, halo8::LDS, s, e, tx8, ty8, b0, bw);
-      else hipLaunchKernelGGL((conv3x3_halo8_kernel<0>), g8, b8, halo8::LDS, s, e, tx8, ty8, b0, bw);
-      const int rc = launch_status();
-      if (rc != RDEIC_OK) return rc;
-      continue;
-    }
-    const int tx = d->w / TC, ty = e.ho / TR;
-    const long tiles = (long)e.n * ty * tx * (d->cout / BN);
-    const dim3 gr((unsigned)tiles), b(NT);
-    if (gm == 2 && fe) hipLaunchKernelGGL((conv3x3_halo_kernel<2, true>), gr, b, LDS, s, e, tx, ty, b0, bw);
-    else if (gm == 2) hipLaunchKernelGGL((conv3x3_halo_kernel<2, false>), gr, b, LDS, s, e, tx, ty, b0, bw);
-    else if (gm == 1 && fe) hipLaunchKernelGGL((conv3x3_halo_kernel<1, true>), gr, b, LDS, s, e, tx, ty, b0, bw);
-    else if (gm == 1) hipLaunchKernelGGL((conv3x3_halo_kernel<1, false>), gr, b, LDS, s, e, tx, ty, b0, bw);
-    else if (fe) hipLaunchKernelGGL((conv3x3_halo_kernel<0, true>), gr, b, LDS, s, e, tx, ty, b0, bw);
-    else hipLaunchKernelGGL((conv3x3_halo_kernel<0, false>), gr, b, LDS, s, e, tx, ty, b0, bw);
+    const int tx = d->w / HALO_TC, ty = e.ho / f.tr;
+    const dim3 grid((unsigned)((long)e.n * ty * tx * (d->cout / HALO_BN)));
+    hipLaunchKernelGGL(f.k[gm][fe], grid, dim3(f.nt), f.lds, s, e, tx, ty, b0, bw);
     const int rc = launch_status();
     if (rc != RDEIC_OK) return rc;
   }

@@ -288,13 +288,8 @@ __global__ __launch_bounds__(256) void gn_apply_vec_kernel(const bf16* __restric
     bf16x8 o;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float4 s = UNIFORM ? sab[q] : p[q];  // (a, b) of channels ch+2q, ch+2q+1
-      float v0 = (float)v[u][2 * q] * s.x + s.y;
-      float v1 = (float)v[u][2 * q + 1] * s.z + s.w;
-      if (silu) {  // x * rcp(1 + e^-x): v_rcp instead of the IEEE divide sequence (bf16 output)
-        v0 *= __builtin_amdgcn_rcpf(1.0f + __expf(-v0));
-        v1 *= __builtin_amdgcn_rcpf(1.0f + __expf(-v1));
-      }
+      float v0 = (float)v[u][2 * q], v1 = (float)v[u][2 * q + 1];
+      gn_fast2(v0, v1, UNIFORM ? sab[q] : p[q], silu);  // (a, b) of channels ch+2q, ch+2q+1
       o[2 * q] = (bf16)(v0 * out_mul);
       o[2 * q + 1] = (bf16)(v1 * out_mul);
     }
@@ -621,13 +616,8 @@ __global__ __launch_bounds__(256) void gn_parts_apply_kernel(const float* __rest
     bf16x8 o;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float4 s = p[q];  // (a, b) of channels ch+2q, ch+2q+1
-      float v0 = (float)v[u][2 * q] * s.x + s.y;
-      float v1 = (float)v[u][2 * q + 1] * s.z + s.w;
-      if (silu) {  // x * rcp(1 + e^-x), as gn_apply_vec_kernel
-        v0 *= __builtin_amdgcn_rcpf(1.0f + __expf(-v0));
-        v1 *= __builtin_amdgcn_rcpf(1.0f + __expf(-v1));
-      }
+      float v0 = (float)v[u][2 * q], v1 = (float)v[u][2 * q + 1];
+      gn_fast2(v0, v1, p[q], silu);  // (a, b) of channels ch+2q, ch+2q+1
       o[2 * q] = (bf16)v0;
       o[2 * q + 1] = (bf16)v1;
     }

@@ -141,3 +141,35 @@ def test_halo8_bit_identical_to_halo4(gpu, n, h, w, cin, cout, silu):
     torch.cuda.synchronize()
     assert torch.equal(outs[0][0], outs[1][0])
     assert torch.equal(outs[0][1], outs[1][1])
+
+
+@pytest.mark.parametrize("res", [True, False])
+@pytest.mark.parametrize("gn,fe", [(0, True), (0, False), (1, False), (2, False)])
+def test_halo4_smallest_case_bit_identical_to_materialised(gpu, gn, fe, res):
+    """The 4-row instantiations no other halo test reaches (the plain conv with the fast epilogue, and every
+    GroupNorm mode with epilogue_vec, taken here through a per-image embedding), on their smallest case:
+    1 x 8 x 64 pixels, 32 -> 128 channels, with and without a residual. With ONE 32-channel block the halo
+    kernel's k order (channel block, tap) is the im2col kernels' (tap, channel) order, and the in-LDS transform
+    writes rdeic_groupnorm_apply's bf16 values, so the output equals the materialised path's bit for bit."""
+    from rdeic_amd import ops
+    torch.manual_seed(10 * gn + fe)
+    x = (torch.randn(1, 8, 64, 32, device="cuda") * 1.5 + 0.3).to(torch.bfloat16)
+    _, _, p = _params(32, 128, seed=41)
+    ab = _gn_ab(x, 8, seed=3) if gn else None
+    r = torch.randn(1, 8, 64, 128, device="cuda").to(torch.bfloat16) if res else None
+    emb = None if fe else torch.randn(1, 128, device="cuda")
+
+    def run(halo):
+        prev6, prev9 = ops.set_halo_conv(2 if halo else 0), ops.set_conv_option(9, 0)  # 4-row form
+        try:
+            n0 = ops.launch_count(ops.COUNT_HALO_CONV)
+            y = ops.conv2d(x, p, gn=ab, gn_silu=gn == 2, emb=emb, res=r)
+            assert (ops.launch_count(ops.COUNT_HALO_CONV) > n0) == halo
+            return y
+        finally:
+            ops.set_halo_conv(prev6)
+            ops.set_conv_option(9, prev9)
+
+    y_h, y_m = run(True), run(False)
+    torch.cuda.synchronize()
+    assert torch.equal(y_h, y_m), (y_h.float() - y_m.float()).abs().max().item()
