@@ -366,7 +366,9 @@ int rdeic_ckbd_dequant(const int32_t* sym, const void* params, int32_t pld, int3
                        int32_t wy, int32_t c, int32_t phase, int64_t img_stride, int64_t off, void* yhat,
                        int32_t yhld, void* anchor_out, int32_t ald, int32_t dtype, void* stream);
 /* Vector quantiser nearest code (compression_modules.py:309-331): given dot[r][j] = z_r.e_j (from
- * rdeic_conv2d), zn = ||z_r||^2, en = ||e_j||^2: idx[r] = first argmin_j (zn[r] + en[j]) - 2 dot[r][j]. */
+ * rdeic_conv2d), zn = ||z_r||^2, en = ||e_j||^2: idx[r] = first argmin_j (zn[r] + en[j]) - 2 dot[r][j].
+ * torch.argmin's rule on non-finite rows: a NaN distance is the minimum and the first NaN wins; a row of
+ * +inf gives 0. idx[r] is always in [0, ncode). */
 int rdeic_vq_argmin(const float* dot, const float* zn, const float* en, int32_t rows, int32_t ncode, int32_t* idx,
                     void* stream);
 /* out[r] = table[idx[r]] (fp32 table, output dtype `dtype`): get_codebook_entry / z_q gather */

@@ -107,6 +107,14 @@ __global__ void ckbd_dequant_kernel(const int32_t* __restrict__ sym, const T* __
   }
 }
 
+// torch.argmin's order on (distance, index) pairs: a NaN distance counts as the minimum, and among
+// equal distances (or among NaNs) the smaller index wins. (INFINITY, INT_MAX) is the identity: it
+// loses to every real pair, so a row of all +inf or all NaN still yields an index in [0, ncode).
+__device__ __forceinline__ bool vq_better(float d, int j, float best, int bi) {
+  if (best != best) return d != d && j < bi;
+  return d != d || d < best || (d == best && j < bi);
+}
+
 // d[r][j] = (zn[r] + en[j]) - 2 * dot[r][j]  (the reference's fp32 op order), first-min argmin per row.
 __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict__ dot, const float* __restrict__ zn,
                                                         const float* __restrict__ en, int rows, int ncode,
@@ -118,7 +126,7 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict_
   const float z = zn[r];
   for (int j = threadIdx.x; j < ncode; j += 256) {
     float d = __fsub_rn(__fadd_rn(z, en[j]), __fmul_rn(2.0f, dr[j]));
-    if (d < best || (d == best && j < bi)) { best = d; bi = j; }
+    if (vq_better(d, j, best, bi)) { best = d; bi = j; }
   }
   __shared__ float sb[256];
   __shared__ int si[256];
@@ -127,7 +135,7 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict_
   for (int s = 128; s > 0; s >>= 1) {
     if (threadIdx.x < s) {
       float ob = sb[threadIdx.x + s]; int oi = si[threadIdx.x + s];
-      if (ob < sb[threadIdx.x] || (ob == sb[threadIdx.x] && oi < si[threadIdx.x])) {
+      if (vq_better(ob, oi, sb[threadIdx.x], si[threadIdx.x])) {
         sb[threadIdx.x] = ob; si[threadIdx.x] = oi;
       }
     }

@@ -473,8 +473,8 @@ def test_conv_splitk_repeatable_with_stats(gpu, cin, cout, hw, B, act, res, emb,
 @pytest.mark.parametrize("levels,sorted_table", [(64, True), (64, False), (300, True), (2, True)])
 def test_ckbd_indexes_scale_table(gpu, levels, sorted_table):
     """rdeic_ckbd_indexes / rdeic_ckbd_encode build_indexes (compressai GaussianConditional: L-1 - #{k: max(s, b) <=
-    table[k]}): the LDS table's binary search on a non-decreasing table and the linear count on any other table
-    (and on tables past the LDS capacity) give the reference's integers exactly, ties at table values included."""
+    table[k]}): build_index's linear count over the table, on a non-decreasing table, a permuted one and one of
+    300 levels, gives the reference's integers exactly, ties at table values included."""
     from rdeic_amd import ops
     g = torch.Generator().manual_seed(levels * 3 + int(sorted_table))
     n, hy, wy, c = 2, 6, 8, 5
