@@ -597,6 +597,35 @@ int rdeic_ac_decode(const uint8_t* data, size_t len, size_t n, const int16_t* cd
 /* The uniform hyper-latent CDF of utils/ckbd.py:117-128 after torchac's int conversion. */
 int rdeic_ac_uniform_cdf(int32_t codebook_size, int16_t* cdf_row);
 
+/* ------------------------------------------------------------ protected streams (fec.cpp)
+ * Reed-Solomon over GF(2^8): field polynomial 0x11d, alpha = 2, generator prod_{i=0}^{nroots-1} (x - alpha^i),
+ * systematic (parity = m(x) x^nroots mod g(x), highest degree first), nroots even in 2..64, at most 255 - nroots
+ * data bytes per codeword, shorter blocks as the shortened code. Host code, reentrant, no HIP runtime.
+ * Block level: the encoder writes the nroots parity bytes of data[n]; the decoder corrects codeword[n_total] (data
+ * then parity) in place, up to nroots / 2 byte errors, writes their number to corrected_out (may be NULL) and
+ * returns 0, or -EBADMSG for an uncorrectable word (left as it came). */
+int rdeic_rs_encode(const uint8_t* data, int32_t n, int32_t nroots, uint8_t* parity_out);
+int rdeic_rs_decode(uint8_t* codeword, int32_t n_total, int32_t nroots, int32_t* corrected_out);
+/* CRC-32 (IEEE 802.3, zlib's): 0xCBF43926 for "123456789". */
+uint32_t rdeic_crc32(const uint8_t* data, size_t n);
+/* Stream level. The protected stream is a 46-byte header codeword ("RDF1", u8 nroots, u8 depth, u32be payload
+ * length, u32be CRC-32 of the payload, 32 parity bytes: 16 byte errors in the header are repaired) and the payload
+ * in codewords of 255 - nroots data bytes (the last may be shorter) + nroots parity bytes, interleaved byte by
+ * byte in groups of `depth` codewords (1..255): 46 + n + nroots * ceil(n / (255 - nroots)) bytes, which is what
+ * the size function returns (0 for bad arguments; payloads up to 2^32 - 1 bytes).
+ * The decoder corrects the header before it reads it, checks the announced length against n and cap before it
+ * uses it, corrects every codeword and checks the CRC. It returns 0 with the payload in dst[0 .. *out_len), or
+ * -EBADMSG (uncorrectable header or codeword, CRC mismatch, a length that disagrees with the header; dst is then
+ * not to be used), -ENOSPC (cap below the announced length), -EINVAL (bad arguments). stats (may be NULL) counts
+ * the codewords looked at (the header's included), the bytes corrected and the uncorrectable codewords. */
+typedef struct rdeic_fec_stats {
+  int32_t codewords, corrected, uncorrectable;
+} rdeic_fec_stats;
+size_t rdeic_fec_encoded_size(size_t n, int32_t nroots, int32_t depth);
+int rdeic_fec_encode(const uint8_t* src, size_t n, int32_t nroots, int32_t depth, uint8_t* dst, size_t cap);
+int rdeic_fec_decode(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len,
+                     rdeic_fec_stats* stats);
+
 /* --------------------------------------------------------- launch profiler
  * The conv / attention / GroupNorm launchers bracket their kernels with HIP events on the
  * launch stream while profiling is on (a preallocated ring of `capacity` event pairs, reused;

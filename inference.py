@@ -1,6 +1,6 @@
 """Command-line codec with the reference's interface (reference inference.py:94-147).
 
-    python inference.py --input DIR --output DIR [--ckpt FILE] [--steps 2] [--seed 231]
+    python inference.py --input DIR --output DIR [--ckpt FILE] [--steps 2] [--seed 231] [--fec rs:NROOTS[:DEPTH]]
 
 Per image: pad to x64 -> compress to `<output>/data/<stem>` (reference file format) ->
 decompress -> q_sample at t=used_timesteps-1 -> relay DDIM -> VAE decode -> crop -> PNG.
@@ -13,6 +13,8 @@ Differences from the reference, all forced by the offline image:
   * the noise draws (x_T, q_sample noise, and the spaced sampler's per-step randn_like) come from a
     seeded CPU generator in the reference's order, not from the device RNG.
 The noise draws follow the reference order (inference.py:64-65: a discarded randn, then noise).
+--fec (not in the reference): `<output>/data/<stem>` is the Reed-Solomon protected stream (rdeic_amd/fec.py), the
+decode starts from it, and bpp includes the protection's overhead. Without the flag nothing changes.
 """
 import os
 import sys
@@ -45,16 +47,20 @@ def list_image_files(img_dir: str, follow_links: bool = True) -> List[str]:
 
 @torch.no_grad()
 def process(model, imgs: List[np.ndarray], sampler: str, steps: int, stream_path: str, guidance_scale: float,
-            c_crossattn: List[torch.Tensor], generator: torch.Generator) -> Tuple[List[np.ndarray], float]:
-    """reference inference.py:22-91 on the HIP path."""
+            c_crossattn: List[torch.Tensor], generator: torch.Generator, fec=None) -> Tuple[List[np.ndarray], float]:
+    """reference inference.py:22-91 on the HIP path. fec: FecParams or a spec; the stream file is then protected."""
     from rdeic_amd.ddim_sampler_relay import DDIMSampler
     from rdeic_amd.spaced_sampler_relay import SpacedSampler
     n = len(imgs)
     control = torch.tensor(np.stack(imgs) / 255.0, dtype=torch.float32).clamp_(0, 1)
     control = control.permute(0, 3, 1, 2).contiguous().to(model.device)
     H, W = control.shape[-2:]
-    bpp = model.apply_condition_compress(control, stream_path, H, W)
-    c_latent, guide_hint = model.apply_condition_decompress(stream_path)
+    if fec is None:
+        bpp = model.apply_condition_compress(control, stream_path, H, W)
+        c_latent, guide_hint = model.apply_condition_decompress(stream_path)
+    else:
+        bpp = model.apply_condition_compress(control, stream_path, H, W, fec=fec)
+        c_latent, guide_hint = model.apply_condition_decompress(stream_path, fec=fec)
     cond = {"c_latent": [c_latent], "c_crossattn": c_crossattn, "guide_hint": guide_hint}
     shape = (n, 4, H // 8, W // 8)
     torch.randn(shape, generator=generator)  # the reference's discarded x_T draw
@@ -88,7 +94,17 @@ def parse_args(argv=None) -> Namespace:
     p.add_argument("--seed", type=int, default=231)
     p.add_argument("--device", type=str, default="cuda", choices=["cuda"])
     p.add_argument("--dtype", type=str, default="fp32", choices=["fp32", "bf16"])
-    return p.parse_args(argv)
+    p.add_argument("--fec", type=str, default="",
+                   help="rs:NROOTS[:DEPTH]: write and decode the Reed-Solomon protected stream; empty = unprotected")
+    args = p.parse_args(argv)
+    args.fec_params = None
+    if args.fec:
+        from rdeic_amd.fec import parse_fec
+        try:
+            args.fec_params = parse_fec(args.fec)
+        except ValueError as e:
+            p.error(str(e))
+    return args
 
 
 def load_model(ckpt: str, dtype: str):
@@ -126,7 +142,7 @@ def main(argv=None) -> None:
         stem = os.path.splitext(name)[0]
         os.makedirs(os.path.join(parent, "data"), exist_ok=True)
         preds, bpp = process(model, [x], args.sampler, args.steps, os.path.join(parent, "data", stem),
-                             args.guidance_scale, c_crossattn, gen)
+                             args.guidance_scale, c_crossattn, gen, fec=args.fec_params)
         out_path = os.path.join(parent, f"{stem}.png")
         Image.fromarray(preds[0][:img.height, :img.width, :]).save(out_path)
         bpps.append(bpp)

@@ -73,6 +73,11 @@ class GemmDesc(C.Structure):
     ]
 
 
+class FecStatsC(C.Structure):
+    """Mirror of rdeic_fec_stats."""
+    _fields_ = [("codewords", C.c_int32), ("corrected", C.c_int32), ("uncorrectable", C.c_int32)]
+
+
 _p, _i32, _i64, _u64, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes). Every symbol of include/rdeic_hip.h appears here.
@@ -188,6 +193,13 @@ PROTOTYPES = {
     "rdeic_ac_encode": (C.c_int, [_p, _sz, _p, _i32, _p, _sz, C.POINTER(_sz)]),
     "rdeic_ac_decode": (C.c_int, [_p, _sz, _sz, _p, _i32, _p]),
     "rdeic_ac_uniform_cdf": (C.c_int, [_i32, _p]),
+    # protected streams (fec.cpp)
+    "rdeic_rs_encode": (C.c_int, [_p, _i32, _i32, _p]),
+    "rdeic_rs_decode": (C.c_int, [_p, _i32, _i32, C.POINTER(_i32)]),
+    "rdeic_crc32": (C.c_uint32, [_p, _sz]),
+    "rdeic_fec_encoded_size": (_sz, [_sz, _i32, _i32]),
+    "rdeic_fec_encode": (C.c_int, [_p, _sz, _i32, _i32, _p, _sz]),
+    "rdeic_fec_decode": (C.c_int, [_p, _sz, _p, _sz, C.POINTER(_sz), C.POINTER(FecStatsC)]),
     # adapter fine-tune step (train.hip)
     "rdeic_gemm_strided": (C.c_int, [C.POINTER(GemmDesc), _p]),
     "rdeic_pack_conv_weight_dgrad": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p]),

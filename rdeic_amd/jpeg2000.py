@@ -87,28 +87,38 @@ def host_score(pred: np.ndarray, target: np.ndarray) -> Dict:
 def run_jpeg2000_robustness(images: Sequence[np.ndarray], image_ids: Sequence[str], target_bpp: float = 0.12,
                             error_type: str = "random", rates: Sequence[float] = (0.0,), seeds: Sequence[int] = (231,),
                             mean_burst_len: float = 8.0, score: Optional[Callable] = None,
-                            recon_cb: Optional[Callable] = None) -> List[Dict]:
+                            recon_cb: Optional[Callable] = None, fec=None) -> List[Dict]:
     """run_jpeg2000_robustness.py:167-276: every uint8 [H,W,3] image is coded once, its codestream corrupted per
     (rate, seed) — rates as fractions — and decoded; one record per (image, rate, seed) with COLUMNS. Any exception
     on decode is the reference's failure row (psnr 0, ssim 0, ms_ssim 0, lpips 1). A decoded size other than the
     original's is resized with LANCZOS (:222-224). score(pred, target) -> {psnr, ssim, ms_ssim, lpips} of two uint8
-    [H,W,3] arrays (host_score by default); recon_cb(record, pred) is called for every decoded row."""
+    [H,W,3] arrays (host_score by default); recon_cb(record, pred) is called for every decoded row.
+    fec (rdeic_amd.fec FecParams or "rs:NROOTS[:DEPTH]"): the protected codestream is what gets corrupted (rate 0
+    included: it is recovered like the others); one that does not recover is a failure row with the FecError's text.
+    bpp is then the protected rate, and every row carries robustness.FEC_COLUMNS after decode_failed."""
     from PIL import Image
     if error_type not in ("random", "burst"):
         raise ValueError(f"error_type {error_type!r} (random | burst)")
     if not available():
         raise RuntimeError("Pillow has no JPEG2000 codec (it was built without OpenJPEG)")
     score = score or host_score
+    from . import fec as F
+    fec = F.as_params(fec)
     records = []
     for img, name in zip(images, image_ids):
         h, w = img.shape[:2]
         clean = encode(img, target_bpp)
         bpp = 8.0 * len(clean) / (h * w)
+        if fec is not None:
+            bpp_payload, clean = bpp, F.protect(clean, fec)
+            bpp = 8.0 * len(clean) / (h * w)
         for rate in rates:
             for seed in seeds:
                 rec = {"codec": "JPEG2000", "image_id": name, "error_type": error_type, "error_rate": rate * 100,
                        "seed": seed, "bpp": bpp, "psnr": 0.0, "ssim": 0.0, "ms_ssim": 0.0, "lpips": 1.0,
                        "decode_failed": True}
+                if fec is not None:
+                    rec.update(fec=fec.spec, bpp_payload=bpp_payload, fec_corrected=0, fec_failed=0)
                 try:
                     if rate == 0:
                         data = clean
@@ -116,6 +126,13 @@ def run_jpeg2000_robustness(images: Sequence[np.ndarray], image_ids: Sequence[st
                         data = bit_flip_bytes(clean, rate, seed)
                     else:
                         data = burst_flip_bytes(clean, rate, mean_burst_len, seed)
+                    if fec is not None:
+                        try:
+                            data, st = F.recover(data)
+                        except F.FecError as e:  # never handed to the JPEG2000 decoder
+                            rec.update(fec_corrected=e.stats.corrected, fec_failed=1)
+                            raise
+                        rec["fec_corrected"] = st.corrected
                     pred = decode(data, MAX_PIXEL_FACTOR * h * w)
                     if pred.shape != img.shape:
                         pred = np.array(Image.fromarray(pred).resize((w, h), Image.LANCZOS))

@@ -216,22 +216,34 @@ class RDEIC:
 
     # ------------------------------------------------------------------ reference API
     @torch.no_grad()
-    def apply_condition_compress(self, x: torch.Tensor, stream_path: str, H: int, W: int) -> float:
-        """x: [1,3,H,W] in [0,1]. Writes the bitstream file, returns bpp = 8*filesize/(H*W)."""
+    def apply_condition_compress(self, x: torch.Tensor, stream_path: str, H: int, W: int, fec=None) -> float:
+        """x: [1,3,H,W] in [0,1]. Writes the bitstream file, returns bpp = 8*filesize/(H*W). fec (rdeic_amd.fec
+        FecParams or "rs:NROOTS[:DEPTH]"): the file is the protected stream, and bpp includes its overhead."""
         if x.shape[0] != 1:
             raise ValueError("apply_condition_compress codes one image per file (the reference's decompress "
                              "supports batch 1 only); use compress_images for batches")
         h = self.encode_nchw_nhwc(x)
         out = self.preprocess_model.compress(h)[0]
         with Path(stream_path).open("wb") as f:
-            bitstream.write_body(f, out["shape"], out["strings"])
+            if fec is None:
+                bitstream.write_body(f, out["shape"], out["strings"])
+            else:
+                from . import fec as F
+                f.write(F.protect(bitstream.pack_body(out["shape"], out["strings"]), fec))
         size = bitstream.filesize(stream_path)
         return float(size) * 8 / (H * W)
 
     @torch.no_grad()
-    def apply_condition_decompress(self, stream_path: str):
+    def apply_condition_decompress(self, stream_path: str, fec=None):
+        """fec: anything but None says the file is a protected stream (never detected from the bytes: a magic number
+        is no evidence on a noisy channel); the code's parameters are read from its corrected header. A stream that
+        cannot be recovered raises rdeic_amd.fec.FecError, a BitstreamError."""
         with Path(stream_path).open("rb") as f:
-            strings, shape = bitstream.read_body(f)
+            if fec is None:
+                strings, shape = bitstream.read_body(f)
+            else:
+                from . import fec as F
+                strings, shape = bitstream.unpack_body(F.recover(f.read())[0])
         c_lat, hint = self.preprocess_model.decompress([strings], shape, device=self.device)
         return ops.nhwc_to_nchw(c_lat), ops.nhwc_to_nchw(hint)
 

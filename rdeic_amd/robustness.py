@@ -239,6 +239,8 @@ LATENT_TYPES = ("mask_replace", "additive")
 COLUMNS = ["image_id", "error_space", "error_type", "error_rate", "seed", "bpp", "psnr", "ssim", "ms_ssim", "lpips",
            "decode_failed"]
 SUMMARY_METRICS = ("psnr", "ssim", "ms_ssim", "lpips")
+# appended after decode_failed by a sweep over protected streams (run_robustness(fec=...)), and only by one
+FEC_COLUMNS = ["fec", "bpp_payload", "fec_corrected", "fec_failed"]
 # plot_robustness.py:136-143: the value a rate's mean has to cross, and on which side failure lies
 THRESHOLDS = {"psnr": 25.0, "ssim": 0.85, "ms_ssim": 0.9, "lpips": 0.3}
 HIGHER_BETTER = {"psnr": True, "ssim": True, "ms_ssim": True, "lpips": False}
@@ -335,7 +337,7 @@ def run_robustness(model, images: torch.Tensor, context: torch.Tensor, error_spa
                    rates: Sequence[float], seeds: Sequence[int], steps: int = 2, sampler: str = "ddpm",
                    noise_seed: int = 231, image_ids: Optional[Sequence[str]] = None, mean_burst_len: float = 8.0,
                    batch_size: int = 8, lpips=None, dists=None, orig_sizes: Optional[Sequence[Tuple[int, int]]] = None,
-                   recon_cb=None, bodies: Optional[Sequence[bytes]] = None) -> List[Dict]:
+                   recon_cb=None, bodies: Optional[Sequence[bytes]] = None, fec=None) -> List[Dict]:
     """The reference's sweep (run_robustness.py:227-350) over uint8 images [B,H,W,3] already padded to multiples of
     64: one record per (image, rate, seed), rates as fractions, in that loop order, with the reference's columns
     (`dists` too with a DISTS model, `error` on a failure row).
@@ -352,8 +354,19 @@ def run_robustness(model, images: torch.Tensor, context: torch.Tensor, error_spa
     176 pixels the old function leaves ssim / ms_ssim None and this one writes NaN, and at 176 and more but no
     multiple of 16 the old one calls ssim_ms_ssim on the whole batch where this one scores SSIM alone (ms_ssim NaN).
     Scores are taken on the crop [:h,:w] of orig_sizes[i] = (h, w) against the cropped original (:311-314).
-    recon_cb(record, crop uint8 [h,w,3] numpy) is called for every decoded row."""
+    recon_cb(record, crop uint8 [h,w,3] numpy) is called for every decoded row.
+
+    fec (rdeic_amd.fec FecParams or "rs:NROOTS[:DEPTH]"; bitstream space only): the stream that crosses the channel is
+    the protected one. `bodies` stay the unprotected bodies; per (rate, seed) the protected stream is corrupted by the
+    same corruptors and seeds, recovered (fec.recover), and only a recovered body reaches decode_isolated. A stream
+    that does not recover is the failure row with the FecError's text as `error`. `bpp` is the protected stream's
+    rate, and every row carries FEC_COLUMNS: fec (the spec), bpp_payload (the body's rate), fec_corrected (bytes the
+    decoder corrected) and fec_failed (0 / 1)."""
     check_error_pair(error_space, error_type)
+    from . import fec as F
+    fec = F.as_params(fec)
+    if fec is not None and error_space != "bitstream":
+        raise ValueError("fec protects the bitstream: it does not go with error_space 'latent'")
     B, H, W, _ = images.shape
     ids = list(image_ids) if image_ids is not None else [f"img{i}" for i in range(B)]
     sizes = [tuple(s) for s in orig_sizes] if orig_sizes is not None else [(H, W)] * B
@@ -362,7 +375,25 @@ def run_robustness(model, images: torch.Tensor, context: torch.Tensor, error_spa
     shape0 = bitstream.unpack_body(bodies[0])[1]
     jobs: List[Tuple[int, Dict]] = []
     payload: List = []
-    if error_space == "bitstream":
+    fec_stats: List = []
+    if fec is not None:
+        protected = [F.protect(b, fec) for b in bodies]
+        recovered = []
+        for i in range(B):
+            for rate in rates:
+                for seed in seeds:
+                    data = Corruptor("bitstream", error_type, rate, seed, mean_burst_len).corrupt_bytes(protected[i])
+                    try:
+                        body, st = F.recover(data)
+                        recovered.append(body)
+                        payload.append(None)
+                    except F.FecError as e:  # never handed to the entropy decoder
+                        st = e.stats
+                        payload.append(e)
+                    fec_stats.append(st)
+        decoded = iter(decode_isolated(model, recovered, shape0, batch_size) if recovered else [])
+        payload = [r if r is not None else next(decoded) for r in payload]
+    elif error_space == "bitstream":
         variants = [Corruptor("bitstream", error_type, rate, seed, mean_burst_len).corrupt_bytes(bodies[i])
                     for i in range(B) for rate in rates for seed in seeds]
         payload = decode_isolated(model, variants, shape0, batch_size)
@@ -373,6 +404,9 @@ def run_robustness(model, images: torch.Tensor, context: torch.Tensor, error_spa
     k = 0
     for i in range(B):
         bpp = 8.0 * len(bodies[i]) / (H * W)  # 8 * filesize / (padded H * W) (run_robustness.py:250-251)
+        bpp_payload = bpp
+        if fec is not None:
+            bpp = 8.0 * len(protected[i]) / (H * W)  # the file a protected codec writes
         for rate in rates:
             for seed in seeds:
                 r = payload[k]
@@ -386,6 +420,9 @@ def run_robustness(model, images: torch.Tensor, context: torch.Tensor, error_spa
                     rec.update(ssim=0.0, ms_ssim=0.0, lpips=1.0, error=f"{type(r).__name__}: {r}")
                     if dists is not None:
                         rec["dists"] = 1.0
+                if fec is not None:
+                    rec.update(fec=fec.spec, bpp_payload=bpp_payload, fec_corrected=fec_stats[k - 1].corrected,
+                               fec_failed=int(isinstance(r, F.FecError)))
                 jobs.append((i, rec))
     ok = [j for j in range(len(jobs)) if not jobs[j][1]["decode_failed"]]
     if ok:
@@ -413,11 +450,13 @@ def run_robustness(model, images: torch.Tensor, context: torch.Tensor, error_spa
 
 def write_records_csv(records: Sequence[Dict], path: str, columns: Optional[Sequence[str]] = None) -> None:
     """The results table of a sweep: COLUMNS (`dists` after `lpips` when the records carry it) or the given
-    columns; a value that was not scored (None) is written as nan."""
+    columns, then FEC_COLUMNS when the records carry them; a value that was not scored (None) is written as nan."""
     import csv
     cols = list(columns) if columns is not None else list(COLUMNS)
     if "dists" not in cols and any("dists" in r for r in records):
         cols.insert(cols.index("lpips") + 1, "dists")
+    if any("fec" in r for r in records):
+        cols += [c for c in FEC_COLUMNS if c not in cols]
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w", newline="") as f:
         w = csv.DictWriter(f, fieldnames=cols, restval=NAN, extrasaction="ignore")
@@ -435,7 +474,7 @@ def read_csv(path: str) -> List[Dict]:
         for row in csv.DictReader(f):
             rec: Dict = {}
             for key, v in row.items():
-                if key in ("image_id", "error_space", "error_type", "codec"):
+                if key in ("image_id", "error_space", "error_type", "codec", "fec"):
                     rec[key] = v
                 elif key == "decode_failed":
                     rec[key] = v.strip().lower() in ("true", "1")
@@ -461,8 +500,10 @@ def _by_rate(records: Sequence[Dict], key: str) -> Dict[float, np.ndarray]:
 def summary_by_rate(records: Sequence[Dict]) -> List[Dict]:
     """The reference's printed table (run_robustness.py:362-370, a groupby on error_rate): per error rate, ascending,
     {"error_rate", "<metric>": (mean, sample std with ddof 1) for psnr / ssim / ms_ssim / lpips, "decode_failed":
-    count}. NaN (and None) values are skipped, as pandas does; a mean of nothing and a std of fewer than two are NaN."""
+    count}. NaN (and None) values are skipped, as pandas does; a mean of nothing and a std of fewer than two are NaN.
+    Where the records carry FEC_COLUMNS a row also has "fec_corrected": the mean, and "fec_failed": the count."""
     cols = {m: _by_rate(records, m) for m in SUMMARY_METRICS}
+    with_fec = any("fec_failed" in r for r in records)
     out = []
     for rate in sorted({float(r["error_rate"]) for r in records}):
         row: Dict = {"error_rate": rate}
@@ -470,6 +511,10 @@ def summary_by_rate(records: Sequence[Dict]) -> List[Dict]:
             v = cols[m][rate]
             row[m] = (float(v.mean()) if v.size else NAN, float(v.std(ddof=1)) if v.size > 1 else NAN)
         row["decode_failed"] = sum(1 for r in records if float(r["error_rate"]) == rate and r["decode_failed"])
+        if with_fec:
+            at = [r for r in records if float(r["error_rate"]) == rate and "fec_failed" in r]
+            row["fec_corrected"] = float(np.mean([r["fec_corrected"] for r in at])) if at else NAN
+            row["fec_failed"] = sum(int(r["fec_failed"]) for r in at)
         out.append(row)
     return out
 
@@ -478,10 +523,16 @@ def format_summary(records: Sequence[Dict]) -> str:
     """summary_by_rate as text, values rounded to 4 places like the reference's `.round(4)`."""
     lines = ["error_rate  " + "  ".join(f"{m + ' mean':>13} {m + ' std':>11}" for m in SUMMARY_METRICS)
              + "  decode_failed"]
-    for row in summary_by_rate(records):
+    table = summary_by_rate(records)
+    with_fec = bool(table) and "fec_failed" in table[0]
+    if with_fec:
+        lines[0] += "  fec_corrected mean  fec_failed"
+    for row in table:
         lines.append(f"{row['error_rate']:>10g}  " + "  ".join(f"{row[m][0]:>13.4f} {row[m][1]:>11.4f}"
                                                               for m in SUMMARY_METRICS)
                      + f"  {row['decode_failed']:>13d}")
+        if with_fec:
+            lines[-1] += f"  {row['fec_corrected']:>18.4f}  {row['fec_failed']:>10d}"
     return "\n".join(lines)
 
 

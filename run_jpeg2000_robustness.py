@@ -4,6 +4,7 @@
         [--rates 0,0.1,0.5,1,2,5,10] [--num_seeds 5] [--burst_len 8.0] [--output_csv indicators/jpeg2000_robustness.csv]
         [--output_dir outputs/jpeg2000_robustness/] [--save_recon] [--seed 231]
         [--lpips_backbone PATH [--lpips_lin PATH]] [--dists_weights PATH [--dists_backbone PATH]]
+        [--fec rs:NROOTS[:DEPTH]]
 
 Every image is coded to JPEG2000 at about --target_bpp (the RDEIC stream's rate), the codestream gets the bit flips
 the RDEIC sweep applies (run_robustness.py), and each decode is scored against the original: the columns codec,
@@ -11,6 +12,10 @@ image_id, error_type, error_rate (percent), seed, bpp, psnr, ssim, ms_ssim, lpip
 the reference (rdeic_amd/jpeg2000.py): the codec is Pillow's bundled OpenJPEG, not the opj_compress / opj_decompress
 tools; a corrupted header that announces more than 4x the original's pixels is a failure row before any pixel is
 decoded; the metrics run on the device (lpips NaN without --lpips_backbone; --dists_weights adds a `dists` column).
+--fec (not in the reference) puts the codestream under the protection run_robustness.py --fec gives the RDEIC stream, so
+that the two codecs are compared under the same code: the protected codestream is corrupted and recovered, one that
+does not recover is a failure row, bpp is the protected rate, and fec, bpp_payload, fec_corrected, fec_failed follow
+decode_failed.
 """
 import os
 import sys
@@ -44,7 +49,16 @@ def parse_args(argv=None) -> Namespace:
                    help="DISTS alpha / beta (.pt / .pth / .npz); adds a dists column after lpips. Empty = no column")
     p.add_argument("--dists_backbone", type=str, default="",
                    help="torchvision VGG16 state dict for DISTS; empty = the convs are read from --dists_weights")
+    p.add_argument("--fec", type=str, default="",
+                   help="rs:NROOTS[:DEPTH]: sweep the Reed-Solomon protected codestream")
     args = p.parse_args(argv)
+    args.fec_params = None
+    if args.fec:
+        from rdeic_amd.fec import parse_fec
+        try:
+            args.fec_params = parse_fec(args.fec)
+        except ValueError as e:
+            p.error(str(e))
     try:
         args.rate_list = [float(r) / 100.0 for r in args.rates.split(",") if r.strip()]
     except ValueError:
@@ -102,6 +116,10 @@ def main(argv=None) -> List[Dict]:
     print(f"Target BPP: {args.target_bpp}")
     print(f"Error rates: {[r * 100 for r in args.rate_list]}%")
     print(f"Error type: {args.error_type}")
+    extra = {}
+    if args.fec_params is not None:
+        print(f"FEC: {args.fec_params.spec}")
+        extra["fec"] = args.fec_params
     os.makedirs(args.output_dir, exist_ok=True)
     records: List[Dict] = []
     for f in files:
@@ -110,7 +128,7 @@ def main(argv=None) -> List[Dict]:
             img = np.array(Image.open(f).convert("RGB"))
             recs = J.run_jpeg2000_robustness([img], [stem], args.target_bpp, args.error_type, args.rate_list, seeds,
                                              args.burst_len, score=score,
-                                             recon_cb=save_recon if args.save_recon else None)
+                                             recon_cb=save_recon if args.save_recon else None, **extra)
             print(f"  {stem}: compressed at {recs[0]['bpp']:.4f} bpp")
             records += recs
         except Exception as e:  # noqa: BLE001

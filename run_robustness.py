@@ -6,7 +6,7 @@
         [--output_csv indicators/robustness_results.csv] [--cache_dir encodings/] [--recon_dir outputs/robustness/]
         [--save_recon] [--force_encode] [--seed 231] [--suppress_warnings]
         [--ckpt FILE] [--dtype fp32|bf16] [--batch_size 8] [--lpips_backbone PATH [--lpips_lin PATH]]
-        [--dists_weights PATH [--dists_backbone PATH]] [--thresholds_dir DIR]
+        [--dists_weights PATH [--dists_backbone PATH]] [--thresholds_dir DIR] [--fec rs:NROOTS[:DEPTH]]
 
 Per image: pad to x64 -> compress once to `<cache_dir>/<stem>` (kept: a later run decodes from that file and does not
 encode again unless --force_encode) -> per (rate, seed) corrupt the stream (bitstream) or the decoded c_latent
@@ -22,7 +22,12 @@ Differences from the reference, all forced by the offline image or by design:
   * every metric runs on the device; lpips is NaN without --lpips_backbone; --dists_weights adds a `dists` column;
   * noise comes from one CPU generator per image seeded --seed (the reference draws on its CUDA generator);
   * --guidance_scale is accepted and, as in the reference (unconditional_conditioning=None), has no effect;
-  * an --error_type that does not go with --error_space is refused at start-up (the reference runs `burst` then).
+  * an --error_type that does not go with --error_space is refused at start-up (the reference runs `burst` then);
+  * --fec (bitstream space only; refused at start-up with --error_space latent): the sweep the reference's study asks
+    for and does not run. The Reed-Solomon protected stream (rdeic_amd/fec.py) is what gets corrupted, by the same
+    corruptors and seeds; it is recovered, then decoded. A stream that does not recover is a failure row. bpp is the
+    protected stream's rate, and the columns fec, bpp_payload, fec_corrected, fec_failed follow decode_failed. The
+    cached `<cache_dir>/<stem>` stays the unprotected body. Without the flag every file, table and print is as before.
 """
 import os
 import sys
@@ -69,7 +74,18 @@ def parse_args(argv=None) -> Namespace:
                    help="torchvision VGG16 state dict for DISTS; empty = the convs are read from --dists_weights")
     p.add_argument("--thresholds_dir", type=str, default="",
                    help="write <error_space>_<error_type>_failure_thresholds.csv / .txt there")
+    p.add_argument("--fec", type=str, default="",
+                   help="rs:NROOTS[:DEPTH]: sweep the Reed-Solomon protected stream (bitstream space only)")
     args = p.parse_args(argv)
+    args.fec_params = None
+    if args.fec:
+        from rdeic_amd.fec import parse_fec
+        if args.error_space != "bitstream":
+            p.error("--fec protects the bitstream: it does not go with --error_space latent")
+        try:
+            args.fec_params = parse_fec(args.fec)
+        except ValueError as e:
+            p.error(str(e))
     from rdeic_amd.robustness import check_error_pair
     try:
         check_error_pair(args.error_space, args.error_type)
@@ -134,6 +150,10 @@ def main(argv=None) -> List[Dict]:
     print(f"Error rates: {[r * 100 for r in args.rate_list]}%")
     print(f"Error space: {args.error_space}, Error type: {args.error_type}")
     print(f"Seeds per rate: {args.num_seeds}")
+    extra = {}
+    if args.fec_params is not None:
+        print(f"FEC: {args.fec_params.spec}")
+        extra["fec"] = args.fec_params
     os.makedirs(args.cache_dir, exist_ok=True)
 
     groups: Dict = {}  # padded size -> files: one size after the other, so every launch plan is recorded once and reused
@@ -171,7 +191,7 @@ def main(argv=None) -> List[Dict]:
                     model, padded, ctx, args.error_space, args.error_type, args.rate_list, seeds, steps=args.steps,
                     sampler=args.sampler, noise_seed=args.seed, image_ids=[stem], mean_burst_len=args.burst_len,
                     batch_size=args.batch_size, lpips=lpips_model, dists=dists_model, orig_sizes=[orig.shape[:2]],
-                    recon_cb=save_recon if args.save_recon else None, bodies=[body])
+                    recon_cb=save_recon if args.save_recon else None, bodies=[body], **extra)
             except Exception as e:  # noqa: BLE001 — one unreadable image does not end the sweep
                 print(f"Error processing {f}: {e}")
     print(f"Encoded {encoded} images, {cached} streams came from {args.cache_dir}")
